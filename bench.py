@@ -1,6 +1,6 @@
 """Contract benchmark: GRIT cross-entropy training throughput on synthetic 640x640 batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -21,7 +21,10 @@ The step runs as ONE captured HIP graph on one rank (grit_amd/engine/graph_step.
 eager launches with the bucketed RCCL all-reduce): two eager warm-up steps, capture, every later step is a copy of the batch into the
 graph's input buffers + one graph launch.  `config.step_graph` says which one ran.
 
-One JSON line on rank 0.  Besides the contract keys:
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the contract keys (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...), the run's config and final_loss; nothing else runs.
+`--dump-outputs DIR` writes, right after the timed steps, what the last of them computed (bench.dump_outputs); the inputs are seeded, so
+two builds given the same arguments can be compared output for output.  `--full` adds, after the timed region:
   roofline      the hand-written kernel FAMILY with the most ms/step among {gemm_nt_bf16 (fused Mlp GEMMs), wgrad_tn (weight gradients),
                 gemm_w4 (persistent long-map GEMM), window-attention backward / forward}, chosen from the measured per-launch times of
                 this run, against the larger of its two bounds (algorithmic flops / 2.5 PFLOP/s, algorithmic bytes / 8 TB/s); both
@@ -106,14 +109,22 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="images per GPU (metric is defined at 32)")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--caption-len", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, what else the benchmark measures: per-launch kernel rooflines and GEMM families, the "
+                         "MSDeformAttn spread micro-benchmark, BASELINE configs 3 and 5, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (the loss, a fixed sample of the trained weights)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline leg")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed steps of the cpu_baseline headline sample (median)")
     ap.add_argument("--fp32", action="store_true", help="diagnostic: no autocast (not the metric's dtype)")
     ap.add_argument("--points", choices=("model", "spread"), default="model",
                     help="spread: MSDeformAttn sampling locations replaced by SURVEY 8d config 2's distribution (diagnostic)")
     ap.add_argument("--ragged", action="store_true", help="diagnostic: images of different sizes (general padding-mask path)")
-    ap.add_argument("--no-analysis", action="store_true", help="skip the post-run analysis steps / micro-benchmarks")
-    return ap.parse_args()
+    ap.add_argument("--no-analysis", action="store_true", help="with --full: skip the post-run analysis steps / micro-benchmarks")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spread_locations(B, Lq, M, L, P, device, seed=0):
@@ -424,6 +435,236 @@ def _keep_stdout_for_the_json_line():
     sys.stdout = os.fdopen(real, "w", buffering=1)
 
 
+def dump_outputs(path, loss, named_params, sample=4 << 20, seed=0):
+    """--dump-outputs: what the last timed step hands its caller, as PATH/<name>.npy -- `loss.npy` (float64 [1], the rank-averaged
+    loss) and `params.npy` (float32: the trained fp32 weights after the step, concatenated in parameter order; above `sample`
+    elements, the values at a fixed seeded set of positions, ascending).  16 MB at most."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.array([loss], dtype=np.float64))
+    flat = torch.cat([p.detach().reshape(-1).float() for _, p in named_params])
+    if flat.numel() > sample:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), sample))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.cpu().numpy())
+
+
+def analysis(args, value, world, events, wa_events, geom_events, gemm_events, event_steps, empty_pair_us):
+    """--full: the keys of the line that the per-launch HIP events of the analysis steps give (rooflines, GEMM families,
+    executed flops), from the events main() collected."""
+    from grit_amd.ops import msda as msda_op
+    roof, msda_bwd = None, None
+    fwd_kind = "fwd" if args.fp32 else "fwd_bf16"
+    fwd = [(a.elapsed_time(b) * 1e-3, n) for kind, a, b, n, _ in events if kind == fwd_kind]
+    bwd = [(a.elapsed_time(b) * 1e-3, n) for kind, a, b, n, _ in events if kind == fwd_kind.replace("fwd", "bwd")]
+    # distinct value-map cells the in-step launches touch, from the sampling locations recorded in the analysis steps
+    cells, whole_map = [], None
+    for kind, a, b, n, geo in geom_events:
+        if kind == fwd_kind and geo is not None:
+            loc, shapes, lsi, B, S, M, esize = geo
+            cells.append(msda_op.unique_lines_touched(loc, shapes.cpu(), lsi.cpu(), S, M))
+            _, Lq, _, L, P, _ = loc.shape
+            whole_map = (B, S, M, 64, L, Lq, P, esize)
+    if fwd:
+        avg_t = sum(t for t, _ in fwd) / len(fwd)
+        whole_bytes = sum(n for _, n in fwd) / len(fwd)  # every tensor once, whole value map (round-1 convention)
+        if cells:
+            B, S, M, D, L, Lq, P, esize = whole_map
+            nbytes = msda_forward_bytes(sum(cells) / len(cells), D * esize, B, Lq, M, D, L, P, esize)
+            basis = ("distinct value-map cells touched by the recorded sampling locations (mean over %d launches: %.1f %% of the "
+                     "map) + locations + weights + output" % (len(cells), 100.0 * sum(cells) / len(cells) * D * esize
+                                                              / (esize * B * S * M * D)))
+        else:  # --no-analysis: no recorded geometry; fall back to PMC traffic so the fraction stays <= 1
+            nbytes, basis = None, "not counted (--no-analysis)"
+        # HBM-side bytes per launch of this kernel at this shape from the committed PMC profile (separate
+        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH_SIZE doubled per the gfx950 note); PMC collection
+        # cannot run inside the timed benchmark, so the figure is quoted only for the shape it was measured on
+        traffic, traffic_src = (pmc_traffic("msda_fwd_bf16_rows4") if (not args.fp32 and args.batch == 32 and args.size == 640
+                                                                       and args.points == "model" and not args.ragged)
+                                else (None, None))
+        achieved = (nbytes if nbytes is not None else (traffic or 0)) / avg_t / 1e9
+        roof = {"bound": "hbm", "kernel": MSDA_FWD_KERNEL[fwd_kind] + ", in the training step", "achieved": achieved,
+                "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                "traffic_source": traffic_src,
+                "traffic_frac": (traffic / avg_t / 1e9 / HBM_PEAK_GBPS) if traffic else None,
+                "launches": len(fwd), "avg_launch_us": avg_t * 1e6,
+                "algorithmic_bytes_per_launch": int(nbytes) if nbytes is not None else None,
+                "algorithmic_bytes_basis": basis, "whole_map_bytes_per_launch": int(whole_bytes),
+                "points": args.points, "empty_event_pair_us": empty_pair_us}
+    if bwd:  # informational: the backward is bound by the chip-wide memory-side atomic rate, not by HBM
+        avg_b = sum(t for t, _ in bwd) / len(bwd)
+        msda_bwd = {"kernel": "msda_bwd_d64 (f32 maps, f32 atomics)" if args.fp32 else
+                    (("msda_bwd_value + msda_bwd_rows4 (gather form: per (image, head) the corner contributions are binned by cell "
+                      "in one CU's LDS and every cell is summed on the matrix cores in f32, rounded to bf16 once; no atomics on "
+                      "memory, dense output)"
+                      if msda_op.F32_METHOD == "sorted" else
+                      "msda_bwd_d64_pk<stage> + msda_stage_flush (f32 atomics into a staging map, one rounding to bf16 per touched cell)")
+                     if msda_op.F32_ACCUMULATE else "msda_bwd_d64_pk (packed-bf16 atomics, same-cell merges)"),
+                    "launches": len(bwd), "avg_launch_us": avg_b * 1e6,
+                    "whole_map_bytes_per_launch": int(bwd[0][1])}
+        if not args.fp32 and msda_op.F32_ACCUMULATE and msda_op.F32_METHOD == "sorted":
+            # the gather form IS an HBM-shaped kernel pair: its compulsory bytes are the dense gradient slice it writes plus
+            # locations, weights, grad_out (twice: both kernels) and the gathered corner rows of the row walk
+            ta, tb = pmc_traffic("msda_bwd_value"), pmc_traffic("msda_bwd_rows4")
+            on_config = args.batch == 32 and args.size == 640 and args.points == "model" and not args.ragged
+            traffic_b = (ta[0] + tb[0]) if (on_config and ta[0] and tb[0]) else None
+            Bm, Sm, Mm, Lm, Lqm, Pm = (int(v) for v in msda_op.LAST_BWD_SHAPE)
+            rows_m, lp_m = Bm * Lqm * Mm, Lm * Pm
+            compulsory = Bm * Sm * Mm * 64 * 2 + rows_m * (lp_m * 12 * 2 + 64 * 2 * 2)
+            msda_bwd.update({"bound": "hbm", "achieved": compulsory / avg_b / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": compulsory / avg_b / 1e9 / HBM_PEAK_GBPS,
+                             "algorithmic_bytes_per_launch": int(compulsory),
+                             "algorithmic_bytes_basis": "dense bf16 gradient slice written once + locations, weights and their "
+                                                        "gradients + grad_out read by both kernels; the gathered corner rows of the "
+                                                        "row walk are NOT counted (a lower bound on the bytes)",
+                             "traffic": traffic_b, "traffic_source": ta[1] if traffic_b else None,
+                             "traffic_frac": (traffic_b / avg_b / 1e9 / HBM_PEAK_GBPS) if traffic_b else None})
+    # window attention against its compulsory HBM bytes (memory-bound at 72 flop/B; the MFMA fraction is informational)
+    window_attention = {}
+    for kind, name, products, tensors in (("fwd", "winattn_fwd", 2, 4), ("bwd", "winattn_bwd", 5, 7)):
+        ev = [(a.elapsed_time(b) * 1e-3, f) for k, a, b, f in wa_events if k == kind]
+        if ev:
+            tt, ff = sum(t for t, _ in ev), sum(f for _, f in ev)
+            units = ff / (products * 2 * 144 * 144 * 32)             # (window, head) pairs over all launches
+            nbytes = units * tensors * 144 * 32 * 2
+            wa_traffic, wa_src = pmc_traffic(name) if (not args.fp32 and args.batch == 32 and args.size == 640
+                                                       and not args.ragged) else (None, None)
+            window_attention[name] = {"bound": "hbm", "kernel": name, "launches_per_step": len(ev) / event_steps,
+                                      "traffic": wa_traffic, "traffic_source": wa_src,
+                                      "traffic_note": "PMC bytes per launch, mean over the launches of a step (stages differ)",
+                                      "algorithmic_bytes_per_launch": int(nbytes / len(ev)),
+                                      "traffic_frac": (wa_traffic / (tt / len(ev)) / 1e9 / HBM_PEAK_GBPS) if wa_traffic else None,
+                                      "ms_per_step": tt / event_steps * 1e3, "avg_launch_us": tt / len(ev) * 1e6,
+                                      "algorithmic_bytes_per_step": int(nbytes / event_steps),
+                                      "algorithmic_bytes_basis": "%d bf16 [144, 32] slices per (window, head)" % tensors,
+                                      "achieved": nbytes / tt / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                      "frac": nbytes / tt / 1e9 / HBM_PEAK_GBPS,
+                                      "achieved_TFLOPs": ff / tt / 1e12, "mfma_frac_bf16": ff / tt / MFMA_PEAK_BF16}
+    # ---- GEMM families of the step, each against BOTH of its bounds (per-launch HIP events in 2 eager steps behind the timed region)
+    FAMILIES = {
+        "gemm_nt_bf16": "gemm_nt_bf16<256,256,64,...> (grit_amd/csrc/gemm.hip): the Swin Mlp's fused GEMMs -- fc1 + bias + GELU "
+                        "writing pre-activation and activation, fc2 input gradient x GELU' + bias-gradient column sums -- and the stage-0 map's "
+                        "narrow products (128 / 384 output columns, K <= 512: HBM streams)",
+        "gemm_w4": "gemm_w4_bf16 (grit_amd/csrc/gemm_w4.hip): persistent four-wave kernel, 128 x 128 / 112 x 128 wave tiles -- every long-map "
+                   "Linear of the step: qkv / proj / fc2 forward (proj and fc2 with the residual epilogue), the NT input gradients of the Swin "
+                   "blocks, PatchMerging, the stacked value projection of the deformable decoder and its input gradient",
+        "gemm_short": "gemm_nt_bf16<64,64,64,4,1,3,E> (grit_amd/csrc/gemm.hip, variant 12): the Linears of the two decoders and the grid net "
+                      "(640 .. 4 800 rows) -- forward + bias and input gradients on transposed weight copies; three workgroups per CU",
+        "wgrad_tn": "wgrad_tn_256 + wgrad_tn_256_grouped (grit_amd/csrc/wgrad_tn.hip): weight gradients dW = dY^T X of the long token "
+                    "maps and, grouped, of the decoders' short ones; fp32 row-slice partials",
+        "wgrad_small": "wgrad_small (grit_amd/csrc/wgrad.hip): 64 x 64-tile grouped weight gradients of shapes outside 256-multiples",
+        "gemm_lib": "hipBLASLt / rocBLAS through torch (tuned table grit_amd/tunableop_gfx950.csv): the sum of gemm_lib_long and "
+                    "gemm_lib_short below",
+        "gemm_lib_long": "NOT an own kernel -- hipBLASLt through torch on the long token maps (>= 8192 rows): what the policies of "
+                         "grit_amd/ops/gemm.py leave there -- the input gradients of input_proj (NN form), K >= 2 048 Linears of the grid net",
+        "gemm_lib_short": "NOT an own kernel -- hipBLASLt / rocBLAS through torch on the short maps (< 8192 rows): what the short-map policy "
+                          "(grit_amd/ops/gemm.py prefers_own_short) leaves of the decoders' Linears -- K >= 2 048, the gate GEMMs, the fp32 "
+                          "vocabulary projection, bias + ReLU fused calls of the detached box refinement",
+    }
+    n_an = 2  # analysis steps the events cover
+    gemm, families = None, {}
+    skipped_flops = skippable_flops = 0.0
+    if gemm_events:
+        def fams_of(kind, pl):
+            if kind == "gemm_lib":  # the aggregate AND its long-map / short-map halves (different regimes: MFMA-bound vs latency)
+                return ("gemm_lib", "gemm_lib_long" if pl.get("rows", 0) >= 8192 else "gemm_lib_short")
+            return (pl.get("kernel", "gemm_nt_bf16"),)
+        for kind, a, b, pl in gemm_events:
+            dt = a.elapsed_time(b) * 1e-3
+            scale = pl.get("row_scale")
+            if scale is not None:  # drop path: 256-row tiles that lie inside dropped samples were not computed
+                rows, per = int(pl["rows"]), int(pl["rows_per_sample"])
+                zero = (scale.detach().float().cpu() == 0)
+                first = torch.arange(0, rows, 256)
+                last = torch.clamp(first + 255, max=rows - 1)
+                lo, hi = first // per, last // per
+                tile_skipped = (lo == hi) & zero[lo]  # the kernel's rule (gemm.hip): the tile lies inside ONE sample, and it is dropped
+                skipped_flops += pl.get("flops", 0.0) * float(tile_skipped.float().mean())
+                skippable_flops += pl.get("flops", 0.0)
+            for name in fams_of(kind, pl):
+                f = families.setdefault(name, {"t": 0.0, "flops": 0.0, "bytes": 0.0, "n": 0})
+                f["t"] += dt
+                f["flops"] += pl.get("flops", 0.0)
+                f["bytes"] += pl.get("bytes", 0.0)
+                f["n"] += 1
+        gemm = {"note": "every GEMM family of the step against BOTH bounds: `frac_mfma` = algorithmic flops / time / 2.5 PFLOP/s (dense bf16), "
+                        "`frac_hbm` = algorithmic bytes (operands once + outputs once + fp32 split partials) / time / 8 TB/s; `bound` names "
+                        "the larger one, `frac` is its value.  Per-launch HIP events on the launch stream in %d eager steps right behind "
+                        "the timed region (an event pair adds ~5 us to a launch); `traffic` = PMC bytes per launch where "
+                        "profiles/r06/pmc_in_step.txt (or an earlier round.s) has the kernel" % n_an}
+        for name, f in families.items():
+            tt = f["t"]
+            fm, fh = f["flops"] / tt / MFMA_PEAK_BF16, f["bytes"] / tt / 1e9 / HBM_PEAK_GBPS
+            traffic, tsrc = pmc_traffic("family:" + name)
+            gemm[name] = {"kernel": FAMILIES.get(name, name), "launches_per_step": f["n"] / n_an, "ms_per_step": tt / n_an * 1e3,
+                          "avg_launch_us": tt / f["n"] * 1e6, "algorithmic_flops_per_launch": f["flops"] / f["n"],
+                          "algorithmic_bytes_per_launch": f["bytes"] / f["n"], "TFLOPs": f["flops"] / tt / 1e12,
+                          "GBps": f["bytes"] / tt / 1e9, "frac_mfma": fm, "frac_hbm": fh, "bound": "mfma" if fm >= fh else "hbm",
+                          "frac": max(fm, fh), "traffic": traffic, "traffic_source": tsrc}
+        own = [v for k, v in gemm.items() if isinstance(v, dict) and not k.startswith("gemm_lib")]
+        for label, sel in (("gemm_own", own), ("all", [v for k, v in gemm.items() if isinstance(v, dict)
+                                                       and k not in ("gemm_lib_long", "gemm_lib_short")])):
+            if sel:
+                tt = sum(v["ms_per_step"] for v in sel) * 1e-3
+                ff = sum(v["algorithmic_flops_per_launch"] * v["launches_per_step"] for v in sel)
+                gemm[label] = {"ms_per_step": tt * 1e3, "PFLOPs": ff / tt / 1e15, "mfma_frac_bf16": ff / tt / MFMA_PEAK_BF16}
+
+    def family_roofline(name):
+        v = gemm.get(name) if gemm else None
+        if not v:
+            return None
+        mf = v["bound"] == "mfma"
+        return {"bound": v["bound"], "kernel": v["kernel"], "launches_per_step": v["launches_per_step"], "ms_per_step": v["ms_per_step"],
+                "avg_launch_us": v["avg_launch_us"],
+                "achieved": v["TFLOPs"] if mf else v["GBps"], "peak": MFMA_PEAK_BF16 / 1e12 if mf else HBM_PEAK_GBPS,
+                "unit": "TFLOP/s" if mf else "GB/s", "frac": v["frac"], "frac_mfma": v["frac_mfma"], "frac_hbm": v["frac_hbm"],
+                "algorithmic_flops_per_launch": v["algorithmic_flops_per_launch"],
+                "algorithmic_bytes_per_launch": v["algorithmic_bytes_per_launch"],
+                "algorithmic_basis": "2 M N K flop per problem; bytes: both operands once, every output map once (two for fc1 + GELU; the "
+                                     "GELU' GEMM also reads the pre-activation map), fp32 row-slice partials of the weight gradients",
+                "traffic": v["traffic"], "traffic_source": v["traffic_source"],
+                "timing": "per-launch HIP events on the launch stream in %d eager steps right behind the timed region" % n_an}
+    roof_wgrad = family_roofline("wgrad_tn")
+    roof_lib_long = family_roofline("gemm_lib_long")
+    # the kernel family with the most time per step -- ALL of them compete (VERDICT r04 #6): the own GEMM families, the two
+    # window-attention kernels AND the library's long-map GEMMs, which the line marks as not an own kernel when they win
+    for r, own_kernel in ((roof_lib_long, False), (roof_wgrad, True)):
+        if r:
+            r["own_kernel"] = own_kernel
+    candidates = [r for r in (family_roofline("gemm_nt_bf16"), roof_wgrad, family_roofline("gemm_w4"), roof_lib_long,
+                              window_attention.get("winattn_bwd"), window_attention.get("winattn_fwd")) if r]
+    for r in candidates:
+        r.setdefault("own_kernel", True)
+    dominant = max(candidates, key=lambda r: r["ms_per_step"]) if candidates else roof
+    if roof:  # MSDeformAttn forward: both denominators side by side
+        roof["frac_touched"] = roof["frac"]
+        roof["frac_compulsory_8d"] = roof["whole_map_bytes_per_launch"] / (roof["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
+        roof["denominators"] = ("frac / frac_touched: distinct value cells the recorded sampling locations reach + locations + weights + "
+                                "output; frac_compulsory_8d: every tensor once incl. the WHOLE value map (SURVEY 8d's figure -- counts "
+                                "cells the kernel never needs)")
+    return {
+        # ... the same with the flops the step EXECUTES: the fused Mlp GEMMs do not compute the 256-row tiles inside samples that drop path
+        # removed from the branch (counted per launch from the drawn factors of the analysis steps)
+        "flops_per_image": {"nominal": FLOP_PER_IMAGE_FWD_BWD,
+                            "executed": FLOP_PER_IMAGE_FWD_BWD - skipped_flops / n_an / args.batch,
+                            "skipped_fraction_of_skippable_gemms": (skipped_flops / skippable_flops) if skippable_flops else 0.0},
+        "mfma_roofline_frac_bf16_executed": value / world * (FLOP_PER_IMAGE_FWD_BWD - skipped_flops / n_an / args.batch) / MFMA_PEAK_BF16,
+        # the hand-written kernel with the most time per step (profiles/r03/*steady_state.txt): the long-map weight-gradient GEMM
+        # (MFMA-bound) once the analysis steps ran, else the window-attention backward (HBM-bound); both are always reported below
+        "roofline": dominant,
+        "roofline_gemm_nt_bf16": family_roofline("gemm_nt_bf16"),
+        "roofline_gemm_w4": family_roofline("gemm_w4"),
+        "roofline_wgrad_tn": roof_wgrad,
+        "roofline_gemm_lib_long": roof_lib_long,
+        "roofline_msda": roof,
+        "msda_backward": msda_bwd,
+        "roofline_winattn_bwd": window_attention.get("winattn_bwd"),
+        "roofline_winattn_fwd": window_attention.get("winattn_fwd"),
+        "gemm": gemm,
+        "config3_bs16": None,
+    }
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -531,8 +772,9 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    msda_op.PROFILE_EVENTS = []
-    wa_op.PROFILE_EVENTS = []
+    # --full: per-launch HIP events of the kernels in eager timed steps (a replayed graph runs no Python and records none)
+    msda_op.PROFILE_EVENTS = [] if args.full else None
+    wa_op.PROFILE_EVENTS = [] if args.full else None
     t0 = time.perf_counter()
     for i in range(args.steps):
         loss = step(args.warmup + i)
@@ -548,8 +790,15 @@ def main():
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
+    if args.dump_outputs:
+        if hasattr(wrapped, "consolidate"):
+            wrapped.consolidate()  # collective, every rank: a no-op unless the optimizer is sharded
+        if rank == 0:
+            dump_outputs(args.dump_outputs, final_loss, wrapped.named_master_parameters() if hasattr(wrapped, "named_master_parameters")
+                         else [(n, p) for n, p in model.named_parameters() if p.requires_grad])
 
-    # ---- after the timed region: analysis steps (every rank takes them: the gradient all-reduce is collective) -----------
+    # ---- after the timed region, --full only: analysis steps (every rank takes them: the gradient all-reduce is collective) --
+    analysed = args.full and not args.no_analysis
     geom_events, gemm_events = [], []
     event_steps = args.steps  # steps the per-launch events of the MSDA / window-attention kernels cover
     if graphed is not None:
@@ -557,7 +806,7 @@ def main():
         # timed in eager steps right behind it (the graph is dropped first; the optimizers go back to launch-argument scalars)
         graphed.release()
         torch.cuda.synchronize()
-        if not args.no_analysis:
+        if analysed:
             msda_op.PROFILE_EVENTS, wa_op.PROFILE_EVENTS = [], []
             event_steps = 3
             for i in range(event_steps):
@@ -565,7 +814,7 @@ def main():
             torch.cuda.synchronize()
             events, msda_op.PROFILE_EVENTS = msda_op.PROFILE_EVENTS, None
             wa_events, wa_op.PROFILE_EVENTS = wa_op.PROFILE_EVENTS, None
-    if not args.no_analysis:
+    if analysed:
         msda_op.PROFILE_EVENTS, msda_op.PROFILE_RECORD_GEOMETRY, profiling.EVENTS = geom_events, True, gemm_events
         for i in range(2):
             eager_step(args.warmup + args.steps + 3 + i)
@@ -574,205 +823,18 @@ def main():
 
     # what an event pair reads with NOTHING between its two markers: the part of every per-launch figure below that is
     # marker / dispatch latency, not kernel time (reported, not subtracted: the roofline figures stay conservative)
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
-    for a, b in pairs:
-        a.record()
-        b.record()
-    torch.cuda.synchronize()
-    empty_pair_us = sorted(a.elapsed_time(b) * 1e3 for a, b in pairs)[len(pairs) // 2]
+    empty_pair_us = None
+    if args.full:
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(64)]
+        for a, b in pairs:
+            a.record()
+            b.record()
+        torch.cuda.synchronize()
+        empty_pair_us = sorted(a.elapsed_time(b) * 1e3 for a, b in pairs)[len(pairs) // 2]
 
     if rank == 0:
         images = world * args.batch * args.steps
         value = images / elapsed
-        roof, msda_bwd = None, None
-        fwd_kind = "fwd" if args.fp32 else "fwd_bf16"
-        fwd = [(a.elapsed_time(b) * 1e-3, n) for kind, a, b, n, _ in events if kind == fwd_kind]
-        bwd = [(a.elapsed_time(b) * 1e-3, n) for kind, a, b, n, _ in events if kind == fwd_kind.replace("fwd", "bwd")]
-        # distinct value-map cells the in-step launches touch, from the sampling locations recorded in the analysis steps
-        cells, whole_map = [], None
-        for kind, a, b, n, geo in geom_events:
-            if kind == fwd_kind and geo is not None:
-                loc, shapes, lsi, B, S, M, esize = geo
-                cells.append(msda_op.unique_lines_touched(loc, shapes.cpu(), lsi.cpu(), S, M))
-                _, Lq, _, L, P, _ = loc.shape
-                whole_map = (B, S, M, 64, L, Lq, P, esize)
-        if fwd:
-            avg_t = sum(t for t, _ in fwd) / len(fwd)
-            whole_bytes = sum(n for _, n in fwd) / len(fwd)  # every tensor once, whole value map (round-1 convention)
-            if cells:
-                B, S, M, D, L, Lq, P, esize = whole_map
-                nbytes = msda_forward_bytes(sum(cells) / len(cells), D * esize, B, Lq, M, D, L, P, esize)
-                basis = ("distinct value-map cells touched by the recorded sampling locations (mean over %d launches: %.1f %% of the "
-                         "map) + locations + weights + output" % (len(cells), 100.0 * sum(cells) / len(cells) * D * esize
-                                                                  / (esize * B * S * M * D)))
-            else:  # --no-analysis: no recorded geometry; fall back to PMC traffic so the fraction stays <= 1
-                nbytes, basis = None, "not counted (--no-analysis)"
-            # HBM-side bytes per launch of this kernel at this shape from the committed PMC profile (separate
-            # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, FETCH_SIZE doubled per the gfx950 note); PMC collection
-            # cannot run inside the timed benchmark, so the figure is quoted only for the shape it was measured on
-            traffic, traffic_src = (pmc_traffic("msda_fwd_bf16_rows4") if (not args.fp32 and args.batch == 32 and args.size == 640
-                                                                           and args.points == "model" and not args.ragged)
-                                    else (None, None))
-            achieved = (nbytes if nbytes is not None else (traffic or 0)) / avg_t / 1e9
-            roof = {"bound": "hbm", "kernel": MSDA_FWD_KERNEL[fwd_kind] + ", in the training step", "achieved": achieved,
-                    "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                    "traffic_source": traffic_src,
-                    "traffic_frac": (traffic / avg_t / 1e9 / HBM_PEAK_GBPS) if traffic else None,
-                    "launches": len(fwd), "avg_launch_us": avg_t * 1e6,
-                    "algorithmic_bytes_per_launch": int(nbytes) if nbytes is not None else None,
-                    "algorithmic_bytes_basis": basis, "whole_map_bytes_per_launch": int(whole_bytes),
-                    "points": args.points, "empty_event_pair_us": empty_pair_us}
-        if bwd:  # informational: the backward is bound by the chip-wide memory-side atomic rate, not by HBM
-            avg_b = sum(t for t, _ in bwd) / len(bwd)
-            msda_bwd = {"kernel": "msda_bwd_d64 (f32 maps, f32 atomics)" if args.fp32 else
-                        (("msda_bwd_value + msda_bwd_rows4 (gather form: per (image, head) the corner contributions are binned by cell "
-                          "in one CU's LDS and every cell is summed on the matrix cores in f32, rounded to bf16 once; no atomics on "
-                          "memory, dense output)"
-                          if msda_op.F32_METHOD == "sorted" else
-                          "msda_bwd_d64_pk<stage> + msda_stage_flush (f32 atomics into a staging map, one rounding to bf16 per touched cell)")
-                         if msda_op.F32_ACCUMULATE else "msda_bwd_d64_pk (packed-bf16 atomics, same-cell merges)"),
-                        "launches": len(bwd), "avg_launch_us": avg_b * 1e6,
-                        "whole_map_bytes_per_launch": int(bwd[0][1])}
-            if not args.fp32 and msda_op.F32_ACCUMULATE and msda_op.F32_METHOD == "sorted":
-                # the gather form IS an HBM-shaped kernel pair: its compulsory bytes are the dense gradient slice it writes plus
-                # locations, weights, grad_out (twice: both kernels) and the gathered corner rows of the row walk
-                ta, tb = pmc_traffic("msda_bwd_value"), pmc_traffic("msda_bwd_rows4")
-                on_config = args.batch == 32 and args.size == 640 and args.points == "model" and not args.ragged
-                traffic_b = (ta[0] + tb[0]) if (on_config and ta[0] and tb[0]) else None
-                Bm, Sm, Mm, Lm, Lqm, Pm = (int(v) for v in msda_op.LAST_BWD_SHAPE)
-                rows_m, lp_m = Bm * Lqm * Mm, Lm * Pm
-                compulsory = Bm * Sm * Mm * 64 * 2 + rows_m * (lp_m * 12 * 2 + 64 * 2 * 2)
-                msda_bwd.update({"bound": "hbm", "achieved": compulsory / avg_b / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                 "frac": compulsory / avg_b / 1e9 / HBM_PEAK_GBPS,
-                                 "algorithmic_bytes_per_launch": int(compulsory),
-                                 "algorithmic_bytes_basis": "dense bf16 gradient slice written once + locations, weights and their "
-                                                            "gradients + grad_out read by both kernels; the gathered corner rows of the "
-                                                            "row walk are NOT counted (a lower bound on the bytes)",
-                                 "traffic": traffic_b, "traffic_source": ta[1] if traffic_b else None,
-                                 "traffic_frac": (traffic_b / avg_b / 1e9 / HBM_PEAK_GBPS) if traffic_b else None})
-        # window attention against its compulsory HBM bytes (memory-bound at 72 flop/B; the MFMA fraction is informational)
-        window_attention = {}
-        for kind, name, products, tensors in (("fwd", "winattn_fwd", 2, 4), ("bwd", "winattn_bwd", 5, 7)):
-            ev = [(a.elapsed_time(b) * 1e-3, f) for k, a, b, f in wa_events if k == kind]
-            if ev:
-                tt, ff = sum(t for t, _ in ev), sum(f for _, f in ev)
-                units = ff / (products * 2 * 144 * 144 * 32)             # (window, head) pairs over all launches
-                nbytes = units * tensors * 144 * 32 * 2
-                wa_traffic, wa_src = pmc_traffic(name) if (not args.fp32 and args.batch == 32 and args.size == 640
-                                                           and not args.ragged) else (None, None)
-                window_attention[name] = {"bound": "hbm", "kernel": name, "launches_per_step": len(ev) / event_steps,
-                                          "traffic": wa_traffic, "traffic_source": wa_src,
-                                          "traffic_note": "PMC bytes per launch, mean over the launches of a step (stages differ)",
-                                          "algorithmic_bytes_per_launch": int(nbytes / len(ev)),
-                                          "traffic_frac": (wa_traffic / (tt / len(ev)) / 1e9 / HBM_PEAK_GBPS) if wa_traffic else None,
-                                          "ms_per_step": tt / event_steps * 1e3, "avg_launch_us": tt / len(ev) * 1e6,
-                                          "algorithmic_bytes_per_step": int(nbytes / event_steps),
-                                          "algorithmic_bytes_basis": "%d bf16 [144, 32] slices per (window, head)" % tensors,
-                                          "achieved": nbytes / tt / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                          "frac": nbytes / tt / 1e9 / HBM_PEAK_GBPS,
-                                          "achieved_TFLOPs": ff / tt / 1e12, "mfma_frac_bf16": ff / tt / MFMA_PEAK_BF16}
-        # ---- GEMM families of the step, each against BOTH of its bounds (per-launch HIP events in 2 eager steps behind the timed region)
-        FAMILIES = {
-            "gemm_nt_bf16": "gemm_nt_bf16<256,256,64,...> (grit_amd/csrc/gemm.hip): the Swin Mlp's fused GEMMs -- fc1 + bias + GELU "
-                            "writing pre-activation and activation, fc2 input gradient x GELU' + bias-gradient column sums -- and the stage-0 map's "
-                            "narrow products (128 / 384 output columns, K <= 512: HBM streams)",
-            "gemm_w4": "gemm_w4_bf16 (grit_amd/csrc/gemm_w4.hip): persistent four-wave kernel, 128 x 128 / 112 x 128 wave tiles -- every long-map "
-                       "Linear of the step: qkv / proj / fc2 forward (proj and fc2 with the residual epilogue), the NT input gradients of the Swin "
-                       "blocks, PatchMerging, the stacked value projection of the deformable decoder and its input gradient",
-            "gemm_short": "gemm_nt_bf16<64,64,64,4,1,3,E> (grit_amd/csrc/gemm.hip, variant 12): the Linears of the two decoders and the grid net "
-                          "(640 .. 4 800 rows) -- forward + bias and input gradients on transposed weight copies; three workgroups per CU",
-            "wgrad_tn": "wgrad_tn_256 + wgrad_tn_256_grouped (grit_amd/csrc/wgrad_tn.hip): weight gradients dW = dY^T X of the long token "
-                        "maps and, grouped, of the decoders' short ones; fp32 row-slice partials",
-            "wgrad_small": "wgrad_small (grit_amd/csrc/wgrad.hip): 64 x 64-tile grouped weight gradients of shapes outside 256-multiples",
-            "gemm_lib": "hipBLASLt / rocBLAS through torch (tuned table grit_amd/tunableop_gfx950.csv): the sum of gemm_lib_long and "
-                        "gemm_lib_short below",
-            "gemm_lib_long": "NOT an own kernel -- hipBLASLt through torch on the long token maps (>= 8192 rows): what the policies of "
-                             "grit_amd/ops/gemm.py leave there -- the input gradients of input_proj (NN form), K >= 2 048 Linears of the grid net",
-            "gemm_lib_short": "NOT an own kernel -- hipBLASLt / rocBLAS through torch on the short maps (< 8192 rows): what the short-map policy "
-                              "(grit_amd/ops/gemm.py prefers_own_short) leaves of the decoders' Linears -- K >= 2 048, the gate GEMMs, the fp32 "
-                              "vocabulary projection, bias + ReLU fused calls of the detached box refinement",
-        }
-        n_an = 2  # analysis steps the events cover
-        gemm, families = None, {}
-        skipped_flops = skippable_flops = 0.0
-        if gemm_events:
-            def fams_of(kind, pl):
-                if kind == "gemm_lib":  # the aggregate AND its long-map / short-map halves (different regimes: MFMA-bound vs latency)
-                    return ("gemm_lib", "gemm_lib_long" if pl.get("rows", 0) >= 8192 else "gemm_lib_short")
-                return (pl.get("kernel", "gemm_nt_bf16"),)
-            for kind, a, b, pl in gemm_events:
-                dt = a.elapsed_time(b) * 1e-3
-                scale = pl.get("row_scale")
-                if scale is not None:  # drop path: 256-row tiles that lie inside dropped samples were not computed
-                    rows, per = int(pl["rows"]), int(pl["rows_per_sample"])
-                    zero = (scale.detach().float().cpu() == 0)
-                    first = torch.arange(0, rows, 256)
-                    last = torch.clamp(first + 255, max=rows - 1)
-                    lo, hi = first // per, last // per
-                    tile_skipped = (lo == hi) & zero[lo]  # the kernel's rule (gemm.hip): the tile lies inside ONE sample, and it is dropped
-                    skipped_flops += pl.get("flops", 0.0) * float(tile_skipped.float().mean())
-                    skippable_flops += pl.get("flops", 0.0)
-                for name in fams_of(kind, pl):
-                    f = families.setdefault(name, {"t": 0.0, "flops": 0.0, "bytes": 0.0, "n": 0})
-                    f["t"] += dt
-                    f["flops"] += pl.get("flops", 0.0)
-                    f["bytes"] += pl.get("bytes", 0.0)
-                    f["n"] += 1
-            gemm = {"note": "every GEMM family of the step against BOTH bounds: `frac_mfma` = algorithmic flops / time / 2.5 PFLOP/s (dense bf16), "
-                            "`frac_hbm` = algorithmic bytes (operands once + outputs once + fp32 split partials) / time / 8 TB/s; `bound` names "
-                            "the larger one, `frac` is its value.  Per-launch HIP events on the launch stream in %d eager steps right behind "
-                            "the timed region (an event pair adds ~5 us to a launch); `traffic` = PMC bytes per launch where "
-                            "profiles/r06/pmc_in_step.txt (or an earlier round.s) has the kernel" % n_an}
-            for name, f in families.items():
-                tt = f["t"]
-                fm, fh = f["flops"] / tt / MFMA_PEAK_BF16, f["bytes"] / tt / 1e9 / HBM_PEAK_GBPS
-                traffic, tsrc = pmc_traffic("family:" + name)
-                gemm[name] = {"kernel": FAMILIES.get(name, name), "launches_per_step": f["n"] / n_an, "ms_per_step": tt / n_an * 1e3,
-                              "avg_launch_us": tt / f["n"] * 1e6, "algorithmic_flops_per_launch": f["flops"] / f["n"],
-                              "algorithmic_bytes_per_launch": f["bytes"] / f["n"], "TFLOPs": f["flops"] / tt / 1e12,
-                              "GBps": f["bytes"] / tt / 1e9, "frac_mfma": fm, "frac_hbm": fh, "bound": "mfma" if fm >= fh else "hbm",
-                              "frac": max(fm, fh), "traffic": traffic, "traffic_source": tsrc}
-            own = [v for k, v in gemm.items() if isinstance(v, dict) and not k.startswith("gemm_lib")]
-            for label, sel in (("gemm_own", own), ("all", [v for k, v in gemm.items() if isinstance(v, dict)
-                                                           and k not in ("gemm_lib_long", "gemm_lib_short")])):
-                if sel:
-                    tt = sum(v["ms_per_step"] for v in sel) * 1e-3
-                    ff = sum(v["algorithmic_flops_per_launch"] * v["launches_per_step"] for v in sel)
-                    gemm[label] = {"ms_per_step": tt * 1e3, "PFLOPs": ff / tt / 1e15, "mfma_frac_bf16": ff / tt / MFMA_PEAK_BF16}
-
-        def family_roofline(name):
-            v = gemm.get(name) if gemm else None
-            if not v:
-                return None
-            mf = v["bound"] == "mfma"
-            return {"bound": v["bound"], "kernel": v["kernel"], "launches_per_step": v["launches_per_step"], "ms_per_step": v["ms_per_step"],
-                    "avg_launch_us": v["avg_launch_us"],
-                    "achieved": v["TFLOPs"] if mf else v["GBps"], "peak": MFMA_PEAK_BF16 / 1e12 if mf else HBM_PEAK_GBPS,
-                    "unit": "TFLOP/s" if mf else "GB/s", "frac": v["frac"], "frac_mfma": v["frac_mfma"], "frac_hbm": v["frac_hbm"],
-                    "algorithmic_flops_per_launch": v["algorithmic_flops_per_launch"],
-                    "algorithmic_bytes_per_launch": v["algorithmic_bytes_per_launch"],
-                    "algorithmic_basis": "2 M N K flop per problem; bytes: both operands once, every output map once (two for fc1 + GELU; the "
-                                         "GELU' GEMM also reads the pre-activation map), fp32 row-slice partials of the weight gradients",
-                    "traffic": v["traffic"], "traffic_source": v["traffic_source"],
-                    "timing": "per-launch HIP events on the launch stream in %d eager steps right behind the timed region" % n_an}
-        roof_wgrad = family_roofline("wgrad_tn")
-        roof_lib_long = family_roofline("gemm_lib_long")
-        # the kernel family with the most time per step -- ALL of them compete: the own GEMM families, the two
-        # window-attention kernels AND the library's long-map GEMMs, which the line marks as not an own kernel when they win
-        for r, own_kernel in ((roof_lib_long, False), (roof_wgrad, True)):
-            if r:
-                r["own_kernel"] = own_kernel
-        candidates = [r for r in (family_roofline("gemm_nt_bf16"), roof_wgrad, family_roofline("gemm_w4"), roof_lib_long,
-                                  window_attention.get("winattn_bwd"), window_attention.get("winattn_fwd")) if r]
-        for r in candidates:
-            r.setdefault("own_kernel", True)
-        dominant = max(candidates, key=lambda r: r["ms_per_step"]) if candidates else roof
-        if roof:  # MSDeformAttn forward: both denominators side by side
-            roof["frac_touched"] = roof["frac"]
-            roof["frac_compulsory_8d"] = roof["whole_map_bytes_per_launch"] / (roof["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS
-            roof["denominators"] = ("frac / frac_touched: distinct value cells the recorded sampling locations reach + locations + weights + "
-                                    "output; frac_compulsory_8d: every tensor once incl. the WHOLE value map (SURVEY 8d's figure -- counts "
-                                    "cells the kernel never needs)")
         out = {
             "metric": _baseline_metric(),
             "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -799,47 +861,31 @@ def main():
                        "step_enqueue": (("one captured HIP graph replayed per step" if graph_plan is None else
                                          "%d captured graph segments per step, the %d bucket all-reduces issued eagerly between them on the "
                                          "process group's stream" % (graph_plan.count('graph'), graph_plan.count('collective')))
-                                        + " (grit_amd/engine/graph_step.py); per-launch kernel events come from %d eager steps behind "
-                                          "the timed region" % event_steps) if graphed is not None
+                                        + " (grit_amd/engine/graph_step.py)"
+                                        + ("; per-launch kernel events come from %d eager steps behind the timed region" % event_steps
+                                           if analysed else "")) if graphed is not None
                        else "eager launches",
                        "rccl_env": rccl_env,
                        "points": args.points, "ragged": bool(args.ragged),
                        "msda_backward_accumulation": ("f32" if args.fp32 else ("f32 (" + msda_op.F32_METHOD + ")") if msda_op.F32_ACCUMULATE
                                                       else "bf16 (packed atomics)")},
             "mfma_roofline_frac_bf16": value / world * FLOP_PER_IMAGE_FWD_BWD / MFMA_PEAK_BF16,
-            # ... the same with the flops the step EXECUTES: the fused Mlp GEMMs do not compute the 256-row tiles inside samples that drop path
-            # removed from the branch (counted per launch from the drawn factors of the analysis steps)
-            "flops_per_image": {"nominal": FLOP_PER_IMAGE_FWD_BWD,
-                                "executed": FLOP_PER_IMAGE_FWD_BWD - skipped_flops / n_an / args.batch,
-                                "skipped_fraction_of_skippable_gemms": (skipped_flops / skippable_flops) if skippable_flops else 0.0},
-            "mfma_roofline_frac_bf16_executed": value / world * (FLOP_PER_IMAGE_FWD_BWD - skipped_flops / n_an / args.batch) / MFMA_PEAK_BF16,
             "final_loss": final_loss,
-            # the hand-written kernel with the most time per step (profiles/r03/*steady_state.txt): the long-map weight-gradient GEMM
-            # (MFMA-bound) once the analysis steps ran, else the window-attention backward (HBM-bound); both are always reported below
-            "roofline": dominant,
-            "roofline_gemm_nt_bf16": family_roofline("gemm_nt_bf16"),
-            "roofline_gemm_w4": family_roofline("gemm_w4"),
-            "roofline_wgrad_tn": roof_wgrad,
-            "roofline_gemm_lib_long": roof_lib_long,
-            "roofline_msda": roof,
-            "msda_backward": msda_bwd,
-            "roofline_winattn_bwd": window_attention.get("winattn_bwd"),
-            "roofline_winattn_fwd": window_attention.get("winattn_fwd"),
-            "gemm": gemm,
-            "config3_bs16": None,
         }
-        if not args.no_analysis:
-            del wrapped, optimizers, model
-            torch.cuda.empty_cache()
-            out["roofline_msda_spread"] = msda_spread_microbench(device)
-            if world == 1:  # config 5 on one GPU, driver-visible (after the timed region, training state released)
-                out["decode_config5"] = decode_config5(device, config)
+        if args.full:
+            out.update(analysis(args, value, world, events, wa_events, geom_events, gemm_events, event_steps, empty_pair_us))
+            if not args.no_analysis:
+                del wrapped, optimizers, model
                 torch.cuda.empty_cache()
-            if world == 1 and not args.fp32 and args.batch == 32 and not args.ragged and args.points == "model":
-                out["config3_bs16"] = config3_child(args)
-        if world == 1 and not args.no_cpu_baseline:
-            torch.cuda.empty_cache()
-            out["cpu_baseline"] = cpu_baseline(config, args.size, args.caption_len, args.cpu_steps)
+                out["roofline_msda_spread"] = msda_spread_microbench(device)
+                if world == 1:  # config 5 on one GPU, driver-visible (after the timed region, training state released)
+                    out["decode_config5"] = decode_config5(device, config)
+                    torch.cuda.empty_cache()
+                if world == 1 and not args.fp32 and args.batch == 32 and not args.ragged and args.points == "model":
+                    out["config3_bs16"] = config3_child(args)
+            if world == 1 and not args.no_cpu_baseline:
+                torch.cuda.empty_cache()
+                out["cpu_baseline"] = cpu_baseline(config, args.size, args.caption_len, args.cpu_steps)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -42,6 +42,13 @@ def disable_drop_path(model):
             m.drop_prob = 0.0
 
 
+def result_manager():
+    """multiprocessing Manager through which spawned workers hand results back.  Its server is a spawned process too: a forked
+    one inherits the HIP state of a test process that already used the GPU, and its garbage collector can crash on freeing the
+    inherited device tensors (the server then dies and the reading test sees EOFError)."""
+    return torch.multiprocessing.get_context("spawn").Manager()
+
+
 def t(a, dtype=None, device="cpu"):
     x = torch.from_numpy(np.ascontiguousarray(a))
     return (x if dtype is None else x.to(dtype)).to(device)

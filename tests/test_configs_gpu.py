@@ -20,7 +20,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from tests.helpers import build_model, disable_drop_path
+from tests.helpers import build_model, disable_drop_path, result_manager
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -118,7 +118,7 @@ def _config4_worker(rank, port, mode, n_images, ret, fill=False, smooth=0):
 
 def _run(worker, *args, extra=()):
     """worker(rank, *args, ret, *extra) in a fresh process; returns what it left in `ret`."""
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(worker, args=args + (ret,) + tuple(extra), nprocs=1, join=True)
         return dict(ret)
@@ -252,11 +252,11 @@ def _a14_worker(rank, world, port, ret):
 
 
 def test_a14_two_ranks_on_the_hip_path_equal_one_process_on_the_whole_batch():
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_a14_worker, args=(2, _free_port(), ret), nprocs=2, join=True)
         two = dict(ret)
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_a14_worker, args=(1, _free_port(), ret), nprocs=1, join=True)
         one = dict(ret)

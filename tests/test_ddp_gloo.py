@@ -10,6 +10,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 from torch import nn
 
+from tests.helpers import result_manager
+
 
 class Toy(nn.Module):
 
@@ -67,7 +69,7 @@ def _worker(rank, world, port, wire_bf16, ret):
 @pytest.mark.parametrize("wire_bf16", [False, True])
 def test_bucketed_allreduce_world2(wire_bf16):
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_worker, args=(2, port, wire_bf16, ret), nprocs=2, join=True)
         ret = dict(ret)
@@ -135,7 +137,7 @@ def test_bf16_compute_fp32_masters_world2():
     """grit_amd.amp.Bf16Compute on two gloo ranks: bf16 flat gradient buckets are all-reduced, fp32 masters stepped by
     Adam stay identical on every rank, compute weights are bf16, the exported state dict is fp32 with module key names."""
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_amp_worker, args=(2, port, ret), nprocs=2, join=True)
         ret = dict(ret)
@@ -155,7 +157,7 @@ def test_bf16_compute_flat_adam_world2_on_gpu():
     rets = []
     for shard in (False, True):
         port = _free_port()
-        with mp.Manager() as mgr:
+        with result_manager() as mgr:
             ret = mgr.dict()
             mp.spawn(_amp_worker, args=(2, port, ret, "cuda", shard), nprocs=2, join=True)
             ret = dict(ret)
@@ -223,7 +225,7 @@ def _phase_worker(rank, world, port, mode, ret):
 @pytest.mark.parametrize("mode", ["repack", "keep_layout"])
 def test_used_set_changes_between_steps_world2(mode):
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_phase_worker, args=(2, port, mode, ret), nprocs=2, join=True)
         ret = dict(ret)
@@ -285,7 +287,7 @@ def test_real_model_bucket_layout_world4():
     averaged gradients equal the mean of the four single-image gradients computed in one process; the layout has a small
     tail bucket and, from the second step on, every bucket's all-reduce is issued before backward returns."""
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_real_worker, args=(4, port, ret), nprocs=4, join=True)
         ret = dict(ret)
@@ -393,7 +395,7 @@ def _shard_worker(rank, world, port, shard, steps, ret):
 
 def _run_shard(world, shard, steps=3):
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         if world == 1:
             _shard_worker(0, 1, port, shard, steps, ret)
@@ -484,7 +486,7 @@ def test_gradient_sync_collectives_on_rccl_one_rank(shard):
     out = []
     for selfc in (False, True):
         port = _free_port()
-        with mp.Manager() as mgr:
+        with result_manager() as mgr:
             ret = mgr.dict()
             mp.spawn(_self_collectives_worker, args=(port, shard, selfc, ret), nprocs=1, join=True)
             out.append(dict(ret))

@@ -21,7 +21,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
-from tests.helpers import build_model
+from tests.helpers import build_model, result_manager
 from tests.test_configs_gpu import DETERMINISTIC, PICKS, _free_port, assert_close_to_fp32_step
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +81,7 @@ def _worker(rank, port, mode, cut_regions, pin_variant, n_images, ret):
 
 
 def _run(*args):
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_worker, args=(_free_port(),) + args + (ret,), nprocs=1, join=True)
         return dict(ret)

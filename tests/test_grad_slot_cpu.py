@@ -12,6 +12,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 from torch import nn
 
+from tests.helpers import result_manager
+
 
 def _contract_ok(M, S):
     gr = 64 if M % 64 == 0 else 32  # wgrad_tn.hip tn_granule
@@ -141,7 +143,7 @@ def _flip_worker(rank, world, port, ret):
 
 def test_live_set_flip_with_in_place_slots_reduces_the_late_gradient():
     port = _free_port()
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_flip_worker, args=(2, port, ret), nprocs=2, join=True)
         ret = dict(ret)

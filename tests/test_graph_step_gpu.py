@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import build_model, disable_drop_path, load, t
+from tests.helpers import build_model, disable_drop_path, load, result_manager, t
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -260,11 +260,11 @@ def test_step_in_segments_around_one_rank_rccl_collectives():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     steps = 20
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_rccl_segments_worker, args=(port, steps, ret), nprocs=1, join=True)
         seg = dict(ret)
-    with mp.Manager() as mgr:
+    with result_manager() as mgr:
         ret = mgr.dict()
         mp.spawn(_eager_reference_worker, args=(steps, ret), nprocs=1, join=True)
         ref = dict(ret)

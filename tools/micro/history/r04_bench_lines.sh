@@ -1,8 +1,8 @@
 # The bench lines and profiles profiles/r04 records next to the headline (run on the GPU box from the repo root).
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04; mkdir -p $O
 cd $R
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 GRIT_STEP_GRAPH=0 timeout 300 python bench.py --no-cpu-baseline --no-analysis --steps 30 --warmup 10 > $O/bench_eager_launches.json 2>/dev/null
 timeout 300 python bench.py --no-cpu-baseline --no-analysis --steps 30 --warmup 10 > $O/bench_graph_step.json 2>/dev/null
 GRIT_GEMM_OWN=0 timeout 300 python bench.py --no-cpu-baseline --no-analysis --steps 30 --warmup 10 > $O/bench_gemm_own_off.json 2>/dev/null

@@ -2,8 +2,8 @@
 # round-6 final records: the driver's command, the default command, rocprofv3 --stats of the default command, the steady-state breakdown, PMC
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command.json 2> $O/bench_driver_command.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/stats_run
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/stats_run -- python3 $R/bench.py --no-cpu-baseline --no-analysis > $O/bench_default_under_rocprof.json 2> $O/rocprof.err

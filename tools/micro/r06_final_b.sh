@@ -1,7 +1,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command_b.json 2> $O/bench_driver_command_b.err
-python3 bench.py > $O/bench_default_b.json 2> $O/bench_default_b.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_command_b.json 2> $O/bench_driver_command_b.err
+python3 bench.py --full > $O/bench_default_b.json 2> $O/bench_default_b.err
 python3 __graft_entry__.py 2>&1 | tail -3
 for f in bench_driver_command_b bench_default_b; do python3 - $O/$f.json <<'PY'
 import json,sys
