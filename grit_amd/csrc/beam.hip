@@ -11,6 +11,10 @@
 #include <stdint.h>
 #include "../../include/grit_hip.h"
 
+// No fused multiply-adds anywhere in this file: the ensemble step's `score + mean * factor` must round twice, as torch's
+// separate mean and add kernels do (the single-map arithmetic has no product next to a sum, so it is unaffected).
+#pragma clang fp contract(off)
+
 namespace {
 
 constexpr int kThreads = 256, kMaxK = 8;
@@ -103,9 +107,62 @@ __device__ __forceinline__ void wave_best(float& v, int& i, int& o) {
     }
 }
 
-template <int KL>  // per-thread list length: k <= KL <= kMaxK (5 for the usual beam of 5: 40 % fewer compare-swaps per insertion)
+// Where the word log-probabilities come from.  OneMap: a single [rows, ld] map (grit_beam_step_f32).  MeanMaps: the average of
+// n <= 8 such maps (grit_beam_step_mean_f32), formed in registers exactly as torch.stack(maps).mean(0) forms it on the device:
+// ATen's MeanOps reduction over the stacked dimension runs in ONE thread per output with four accumulators (Reduce.cuh
+// thread_reduce_impl, vt0 = 4: map m goes to accumulator m % 4, each starting from 0), combined as ((a0 + a1) + a2) + a3 and
+// projected by a MULTIPLY with factor = float(outputs) / float(inputs) (ReduceMomentKernel.cu mean_kernel_impl).
+constexpr int kMaxMaps = 8;
+struct MapTable { const float* p[kMaxMaps]; };  // by value in the kernel arguments: nothing to upload, nothing to keep alive
+
+struct OneMap {
+    const float* p;
+    __device__ __forceinline__ float at(size_t i) const { return p[i]; }
+    __device__ __forceinline__ bool aligned16(size_t i) const { return (((uintptr_t)(p + i)) & 15) == 0; }
+    __device__ __forceinline__ float4 at4(size_t i) const { return *reinterpret_cast<const float4*>(p + i); }
+};
+
+struct MeanMaps {
+    MapTable t;
+    int n;
+    float factor;
+    __device__ __forceinline__ float at(size_t i) const {
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int m = 0; m < kMaxMaps; ++m)
+            if (m < n) a[m & 3] = a[m & 3] + t.p[m][i];
+        return (((a[0] + a[1]) + a[2]) + a[3]) * factor;
+    }
+    __device__ __forceinline__ bool aligned16(size_t i) const {
+        uintptr_t bits = 0;
+#pragma unroll
+        for (int m = 0; m < kMaxMaps; ++m)
+            if (m < n) bits |= (uintptr_t)(t.p[m] + i);
+        return (bits & 15) == 0;
+    }
+    __device__ __forceinline__ float4 at4(size_t i) const {
+        float4 a[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int m = 0; m < kMaxMaps; ++m)
+            if (m < n) {
+                const float4 x = *reinterpret_cast<const float4*>(t.p[m] + i);
+                float4& s = a[m & 3];
+                s.x = s.x + x.x; s.y = s.y + x.y; s.z = s.z + x.z; s.w = s.w + x.w;
+            }
+        float4 r;
+        r.x = (((a[0].x + a[1].x) + a[2].x) + a[3].x) * factor;
+        r.y = (((a[0].y + a[1].y) + a[2].y) + a[3].y) * factor;
+        r.z = (((a[0].z + a[1].z) + a[2].z) + a[3].z) * factor;
+        r.w = (((a[0].w + a[1].w) + a[2].w) + a[3].w) * factor;
+        return r;
+    }
+};
+
+template <int KL, class Src>  // per-thread list length: k <= KL <= kMaxK (5 for the usual beam of 5: 40 % fewer compare-swaps per insertion)
 __global__ __launch_bounds__(kBeamThreads)
-void beam_partial(const float* __restrict__ logp, long ld, const float* __restrict__ seq_lp, const float* __restrict__ seq_mask,
+void beam_partial(Src logp, long ld, const float* __restrict__ seq_lp, const float* __restrict__ seq_mask,
                   const int64_t* __restrict__ prev_words, int eos, int first_step, int cur, int V, int k, int parts,
                   float* __restrict__ ws_val, int* __restrict__ ws_idx) {
     __shared__ float sv[2][kBeamThreads / 64];
@@ -117,7 +174,7 @@ void beam_partial(const float* __restrict__ logp, long ld, const float* __restri
     const float base = seq_lp[row_id];
     bool alive = true;
     if (!first_step) alive = (seq_mask[row_id] * (prev_words[row_id] != (int64_t)eos ? 1.f : 0.f)) != 0.f;
-    const float* row = logp + (size_t)row_id * ld;
+    const size_t row = (size_t)row_id * ld;
     const int seg = ((V + parts - 1) / parts + 3) & ~3;
     const int v0 = part * seg, v1 = min(V, v0 + seg);
     float bv[KL];
@@ -136,18 +193,17 @@ void beam_partial(const float* __restrict__ logp, long ld, const float* __restri
     };
     const int flat0 = j * V;
     if (alive) {
-        const bool vec = (((uintptr_t)(row + v0)) & 15) == 0;
+        const bool vec = logp.aligned16(row + v0);
         if (vec) {
             const int n4 = (v1 - v0) >> 2;
-            const float4* r4 = reinterpret_cast<const float4*>(row + v0);
             for (int i = tid; i < n4; i += kBeamThreads) {
-                const float4 t = r4[i];
+                const float4 t = logp.at4(row + v0 + 4 * i);
                 const int e = flat0 + v0 + 4 * i;
                 push(base + t.x, e); push(base + t.y, e + 1); push(base + t.z, e + 2); push(base + t.w, e + 3);
             }
-            for (int v = v0 + 4 * n4 + tid; v < v1; v += kBeamThreads) push(base + row[v], flat0 + v);
+            for (int v = v0 + 4 * n4 + tid; v < v1; v += kBeamThreads) push(base + logp.at(row + v), flat0 + v);
         } else {
-            for (int v = v0 + tid; v < v1; v += kBeamThreads) push(base + row[v], flat0 + v);
+            for (int v = v0 + tid; v < v1; v += kBeamThreads) push(base + logp.at(row + v), flat0 + v);
         }
     } else {
         // a finished beam survives only through vocabulary index 0; the other entries all score -999 (ties by index)
@@ -176,8 +232,9 @@ void beam_partial(const float* __restrict__ logp, long ld, const float* __restri
     }
 }
 
+template <class Src>
 __global__ __launch_bounds__(64)
-void beam_merge(const float* __restrict__ logp, long ld, const float* __restrict__ seq_mask, const int64_t* __restrict__ prev_words,
+void beam_merge(Src logp, long ld, const float* __restrict__ seq_mask, const int64_t* __restrict__ prev_words,
                 int eos, int first_step, int cur, int V, int k, int parts, const float* __restrict__ ws_val,
                 const int* __restrict__ ws_idx, int64_t* __restrict__ sel_beam, int64_t* __restrict__ sel_word,
                 float* __restrict__ new_lp, float* __restrict__ new_mask, float* __restrict__ picked) {
@@ -208,7 +265,7 @@ void beam_merge(const float* __restrict__ logp, long ld, const float* __restrict
             const size_t at = (size_t)b * k + r;
             sel_beam[at] = jb; sel_word[at] = word;
             new_lp[at] = bvv; new_mask[at] = alive;
-            picked[at] = logp[(size_t)row_id * ld + word] * alive;
+            picked[at] = logp.at((size_t)row_id * ld + word) * alive;
         }
     }
 }
@@ -221,11 +278,13 @@ extern "C" long grit_beam_step_workspace(int B, int cur_beam, int k) {
     return (long)B * cur_beam * parts * kMaxK * 8;
 }
 
-extern "C" int grit_beam_step_f32(const float* logp, long ld, const float* seq_logprob, const float* seq_mask,
-                                  const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                                  void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-                                  float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
-    if (!logp || !seq_logprob || !workspace || !sel_beam || !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob ||
+namespace {
+
+template <class Src>
+int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos, int first_step,
+              int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
+              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
+    if (!seq_logprob || !workspace || !sel_beam || !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob ||
         B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V)
         return GRIT_ERR_BAD_ARG;
     if (!first_step && (!seq_mask || !prev_words)) return GRIT_ERR_BAD_ARG;
@@ -236,14 +295,46 @@ extern "C" int grit_beam_step_f32(const float* logp, long ld, const float* seq_l
     float* ws_val = reinterpret_cast<float*>(workspace);
     int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)B * cur_beam * parts * kMaxK);
     if (k <= 5)
-        hipLaunchKernelGGL(beam_partial<5>, dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, logp, ld, seq_logprob,
-                           seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    else
-        hipLaunchKernelGGL(beam_partial<kMaxK>, dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, logp, ld,
+        hipLaunchKernelGGL((beam_partial<5, Src>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld,
                            seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    hipLaunchKernelGGL(beam_merge, dim3(B), dim3(64), 0, (hipStream_t)stream, logp, ld, seq_mask, prev_words, eos, first_step,
+    else
+        hipLaunchKernelGGL((beam_partial<kMaxK, Src>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld,
+                           seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
+    hipLaunchKernelGGL(beam_merge<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_mask, prev_words, eos, first_step,
                        cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int grit_beam_step_f32(const float* logp, long ld, const float* seq_logprob, const float* seq_mask,
+                                  const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                                  void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
+                                  float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
+    if (!logp) return GRIT_ERR_BAD_ARG;
+    return beam_step(OneMap{logp}, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
+                     workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
+}
+
+extern "C" int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob,
+                                       const float* seq_mask, const int64_t* prev_words, int eos, int first_step, int B,
+                                       int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam,
+                                       int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
+                                       void* stream) {
+    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0) return GRIT_ERR_BAD_ARG;
+    if (n_maps > kMaxMaps) return GRIT_ERR_UNSUPPORTED;
+    MeanMaps src{};
+    for (int m = 0; m < n_maps; ++m) {
+        if (!maps[m]) return GRIT_ERR_BAD_ARG;
+        src.t.p[m] = maps[m];
+    }
+    src.n = n_maps;
+    // torch: static_cast<float>(iter.num_output_elements()) / iter.numel() -- float(N) / float(K * N), not 1 / K (they differ once
+    // K * N is no longer exact in float)
+    const long outputs = (long)B * cur_beam * V;
+    src.factor = (float)outputs / (float)(outputs * n_maps);
+    return beam_step(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace, workspace_bytes,
+                     sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
 }
 
 extern "C" int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t* idx_out, float* val_out, void* stream) {

@@ -79,8 +79,17 @@ def gather_result(value):
     return value
 
 
+def _refuse_ensemble_checkpoint(model):
+    """An Ensemble's state dict (keys `models.<i>.…`) is no checkpoint the single-model loaders read: refused, not written."""
+    from grit_amd.models.caption.ensemble import Ensemble
+    if isinstance(_unwrap(model), Ensemble):
+        raise ValueError("an Ensemble has no single-model checkpoint: save each of its members instead (evaluate_metrics of "
+                         "an Ensemble needs best_cider=None or log_and_save=False)")
+
+
 def save_checkpoint(model, optimizers, epoch, scores, best_ciders, config=None, filename='checkpoint_last.pth',
                     scheduler=None):
+    _refuse_ensemble_checkpoint(model)
     torch.save(
         {
             "state_dict": (model.master_state_dict() if hasattr(model, 'master_state_dict')
@@ -235,7 +244,10 @@ def train_xe(model, dataloaders, optimizers, text_field, epoch, rank=0, config=N
 def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='test', config=None, train_res=None,
                      writer=None, best_cider=None, which='ft_xe', scheduler=None, log_and_save=True, scorer=None):
     """Beam-search every batch (reference :165-183) and hand tokens to `scorer(gts, gen) -> dict` if given.
-    Returns (token tensors per batch, seconds per batch) when no scorer is supplied."""
+    Returns (token tensors per batch, seconds per batch) when no scorer is supplied.  `model` may be an Ensemble
+    (models/caption/ensemble.py); it cannot save a best checkpoint, so with one best_cider must be None (or log_and_save False)."""
+    if log_and_save and best_cider is not None:
+        _refuse_ensemble_checkpoint(model)  # before the evaluation, not after it
     model.eval()
     times, tokens, gen, gts = [], [], {}, {}
     for it, batch in enumerate(_progress(dataloader, desc=f'Epoch {epoch} - evaluation on {split}', unit='it')):

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgrit_hip.so")
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 _c = ctypes
 _ptr, _int, _i64, _f32, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -88,6 +88,8 @@ SIGNATURES = {
     "grit_beam_step_workspace": [_int, _int, _int],
     "grit_beam_step_f32": [_ptr, _c.c_long, _ptr, _ptr, _ptr, _int, _int, _int, _int, _int, _int, _ptr, _c.c_long,
                            _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "grit_beam_step_mean_f32": [_ptr, _int, _c.c_long, _ptr, _ptr, _ptr, _int, _int, _int, _int, _int, _int, _ptr, _c.c_long,
+                                _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     "grit_gemm_bf16_nt": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _ptr, _int, _ptr],
     "grit_gemm_w4_tile_rows": [_int, _int],
     "grit_gemm_bf16_nt_res": [_ptr, _c.c_long] * 3 + [_int] * 3 + [_ptr, _ptr, _c.c_long, _ptr, _int, _ptr],

@@ -9,6 +9,7 @@ re-sorted by score.
 """
 import ctypes
 import os
+from contextlib import contextmanager
 
 import torch
 from torch import nn
@@ -28,7 +29,109 @@ _GRAPH_DECODE = os.environ.get('GRIT_GRAPH_DECODE', '1') != '0'
 _FUSED_BEAM_STEP = os.environ.get('GRIT_FUSED_BEAM_STEP', '1') != '0'
 
 
-class Transformer(BaseCaptioner):
+class BeamSearchSteps(object):
+    """Beam bookkeeping shared by Transformer and Ensemble (models/caption/ensemble.py): the search object keeps seq_mask,
+    seq_logprob, log_probs, selected_words (and all_log_probs) of the running search; `members` are the captioners whose
+    registered states follow the surviving beams (the Transformer itself, or every model of an ensemble)."""
+
+    def _beam_result(self, outputs, batch_size, beam_size, max_len, out_size, return_probs):
+        _, order = torch.sort(self.seq_logprob, 1, descending=True)
+        idx = order.expand(batch_size, beam_size, max_len)
+        outputs = torch.gather(torch.cat(outputs, -1), 1, idx)
+        log_probs = torch.gather(torch.cat(self.log_probs, -1), 1, idx)
+        outputs, log_probs = outputs.contiguous()[:, :out_size], log_probs.contiguous()[:, :out_size]
+        if out_size == 1:
+            outputs, log_probs = outputs.squeeze(1), log_probs.squeeze(1)
+        if not return_probs:
+            return outputs, log_probs
+        all_lp = torch.cat(self.all_log_probs, 2)
+        all_lp = torch.gather(all_lp, 1, order.unsqueeze(-1).expand(batch_size, beam_size, max_len, all_lp.shape[-1]))
+        return outputs, log_probs, all_lp
+
+    def select(self, t, candidate_logprob, beam_size, **kwargs):
+        """[B, Beam, V] -> the `beam_size` best of the flattened candidates, best first.  The reference takes the head of
+        a full descending torch.sort over beam*V = 51 005 scores per image per step (transformer.py:184-188); the selection
+        kernel (grit_topk_rows_f32: one workgroup per image, the row read once) returns the same values in the same order --
+        the order among exactly tied scores is unspecified in the reference and is by ascending index here."""
+        flat = candidate_logprob.reshape(candidate_logprob.shape[0], -1)
+        if flat.is_cuda and flat.dtype == torch.float32 and beam_size <= 8 and not flat.requires_grad \
+                and backend.override() is None:
+            flat = flat if flat.stride(1) == 1 else flat.contiguous()
+            idx = torch.empty((flat.shape[0], beam_size), dtype=torch.int64, device=flat.device)
+            logprob = torch.empty((flat.shape[0], beam_size), dtype=torch.float32, device=flat.device)
+            with _lib.device_guard(flat.device):
+                st = _lib.load().grit_topk_rows_f32(ctypes.c_void_p(flat.data_ptr()), flat.stride(0), flat.shape[0],
+                                                    flat.shape[1], beam_size, ctypes.c_void_p(idx.data_ptr()),
+                                                    ctypes.c_void_p(logprob.data_ptr()), _lib.current_stream_ptr())
+            _lib.check(st, "grit_topk_rows_f32")
+            return idx, logprob
+        # with gradient (self-critical training), on the CPU (oracle runs) and for wide beams: the library selection
+        logprob, idx = torch.topk(flat, beam_size, dim=-1, largest=True, sorted=True)
+        return idx, logprob
+
+    def _expand_state(self, selected_beam, cur_beam_size, batch_size, beam_size):
+        """state [B*cur_beam, ...] -> rows of the surviving beams [B*beam, ...]."""
+
+        def fn(tensor):
+            tail = [int(s) for s in tensor.shape[1:]]
+            index = selected_beam.view(batch_size, beam_size, *([1] * len(tail))).expand(batch_size, beam_size, *tail)
+            picked = torch.gather(tensor.view(batch_size, cur_beam_size, *tail), 1, index)
+            return picked.view(-1, *tail)
+
+        return fn
+
+    def _beam_advance(self, members, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size, eos_idx,
+                      **kwargs):
+        """The body of `iter` after the word log-probabilities word_logprob [B, cur_beam, V]: `fused` holds what the fused step
+        returned (sel_beam, sel_word, seq_logprob, seq_mask, picked), or is None for the composed torch form."""
+        cur_beam = 1 if timestep == 0 else beam_size
+        if fused is not None:
+            selected_beam, selected_words, seq_logprob, seq_mask, picked = fused
+        else:
+            V = word_logprob.shape[-1]
+            candidates = self.seq_logprob + word_logprob
+            if timestep > 0:
+                alive = (self.selected_words.view(batch_size, cur_beam) != eos_idx).float().unsqueeze(-1)
+                self.seq_mask = self.seq_mask * alive
+                word_logprob = word_logprob * self.seq_mask
+                frozen = self.seq_logprob.expand_as(candidates).contiguous()
+                frozen[:, :, 1:] = -999  # a finished beam survives only through vocabulary index 0
+                candidates = self.seq_mask * candidates + frozen * (1 - self.seq_mask)
+
+            selected_idx, selected_logprob = self.select(timestep, candidates, beam_size, **kwargs)
+            selected_beam = torch.div(selected_idx, V, rounding_mode='floor')
+            selected_words = selected_idx - selected_beam * V
+
+        for m in members:
+            m._follow_beams(selected_beam, cur_beam, batch_size, beam_size)
+
+        beam_col = selected_beam.unsqueeze(-1)
+        if fused is not None:
+            self.seq_logprob, self.seq_mask = seq_logprob, seq_mask
+        else:
+            self.seq_logprob = selected_logprob.unsqueeze(-1)
+            self.seq_mask = torch.gather(self.seq_mask, 1, beam_col)
+        # the history of every surviving beam moves with it: ONE gather of the concatenated columns instead of one per past
+        # step (the lists hold a single [B, beam, t] tensor from step 1 on)
+        if outputs:
+            hist = outputs[0] if len(outputs) == 1 else torch.cat(outputs, -1)
+            outputs = [torch.gather(hist, 1, beam_col.expand(batch_size, beam_size, hist.shape[-1]))]
+        outputs.append(selected_words.unsqueeze(-1))
+        if return_probs:
+            lp = word_logprob.expand((batch_size, beam_size, -1)) if timestep == 0 else word_logprob
+            self.all_log_probs.append(lp.unsqueeze(2))
+        if fused is None:
+            picked = torch.gather(word_logprob, 1, beam_col.expand(batch_size, beam_size, V))
+            picked = torch.gather(picked, 2, selected_words.unsqueeze(-1))
+        if self.log_probs:
+            hist = self.log_probs[0] if len(self.log_probs) == 1 else torch.cat(self.log_probs, -1)
+            self.log_probs = [torch.gather(hist, 1, beam_col.expand(batch_size, beam_size, hist.shape[-1]))]
+        self.log_probs.append(picked)
+        self.selected_words = selected_words.view(-1, 1)
+        return outputs
+
+
+class Transformer(BeamSearchSteps, BaseCaptioner):
 
     def __init__(self, detector, config=None):
         super().__init__()
@@ -145,6 +248,16 @@ class Transformer(BaseCaptioner):
         if return_probs:
             self.all_log_probs = []
         outputs = []
+        with self._decode_session(batch_size):
+            for t in range(max_len):
+                images, outputs = self.iter(timestep=t, samples=images, outputs=outputs, return_probs=return_probs,
+                                            batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, **kwargs)
+        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs)
+
+    @contextmanager
+    def _decode_session(self, batch_size):
+        """Stateful mode for one beam search of `batch_size` images, with the decoder's per-search caches armed (hoisted
+        cross-attention K/V, fused self-attention K/V append) and disarmed again afterwards."""
         cross = [m.attention for layer in self.cap_generator.layers for m in (layer.vis_att1, layer.vis_att2)]
         try:
             for att in cross:  # N1: project the visual memory once per beam layout instead of once per step
@@ -152,24 +265,10 @@ class Transformer(BaseCaptioner):
             for m in self._kv_cached_modules():
                 m._kv_deferred, m._beam_src = False, None
             with self.statefulness(batch_size):
-                for t in range(max_len):
-                    images, outputs = self.iter(timestep=t, samples=images, outputs=outputs, return_probs=return_probs,
-                                                batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, **kwargs)
+                yield
         finally:
             for att in cross:
                 att.hoist_kv, att._kv = False, None
-        _, order = torch.sort(self.seq_logprob, 1, descending=True)
-        idx = order.expand(batch_size, beam_size, max_len)
-        outputs = torch.gather(torch.cat(outputs, -1), 1, idx)
-        log_probs = torch.gather(torch.cat(self.log_probs, -1), 1, idx)
-        outputs, log_probs = outputs.contiguous()[:, :out_size], log_probs.contiguous()[:, :out_size]
-        if out_size == 1:
-            outputs, log_probs = outputs.squeeze(1), log_probs.squeeze(1)
-        if not return_probs:
-            return outputs, log_probs
-        all_lp = torch.cat(self.all_log_probs, 2)
-        all_lp = torch.gather(all_lp, 1, order.unsqueeze(-1).expand(batch_size, beam_size, max_len, all_lp.shape[-1]))
-        return outputs, log_probs, all_lp
 
     def step(self, timestep, prev_output, samples, seq, mode='teacher_forcing', **kwargs):
         if mode != 'feedback':
@@ -204,38 +303,6 @@ class Transformer(BaseCaptioner):
     def init_state(self, batch_size, device):
         return [torch.zeros((batch_size, 0), dtype=torch.long, device=device), None, None]
 
-    def select(self, t, candidate_logprob, beam_size, **kwargs):
-        """[B, Beam, V] -> the `beam_size` best of the flattened candidates, best first.  The reference takes the head of
-        a full descending torch.sort over beam*V = 51 005 scores per image per step (transformer.py:184-188); the selection
-        kernel (grit_topk_rows_f32: one workgroup per image, the row read once) returns the same values in the same order --
-        the order among exactly tied scores is unspecified in the reference and is by ascending index here."""
-        flat = candidate_logprob.reshape(candidate_logprob.shape[0], -1)
-        if flat.is_cuda and flat.dtype == torch.float32 and beam_size <= 8 and not flat.requires_grad \
-                and backend.override() is None:
-            flat = flat if flat.stride(1) == 1 else flat.contiguous()
-            idx = torch.empty((flat.shape[0], beam_size), dtype=torch.int64, device=flat.device)
-            logprob = torch.empty((flat.shape[0], beam_size), dtype=torch.float32, device=flat.device)
-            with _lib.device_guard(flat.device):
-                st = _lib.load().grit_topk_rows_f32(ctypes.c_void_p(flat.data_ptr()), flat.stride(0), flat.shape[0],
-                                                    flat.shape[1], beam_size, ctypes.c_void_p(idx.data_ptr()),
-                                                    ctypes.c_void_p(logprob.data_ptr()), _lib.current_stream_ptr())
-            _lib.check(st, "grit_topk_rows_f32")
-            return idx, logprob
-        # with gradient (self-critical training), on the CPU (oracle runs) and for wide beams: the library selection
-        logprob, idx = torch.topk(flat, beam_size, dim=-1, largest=True, sorted=True)
-        return idx, logprob
-
-    def _expand_state(self, selected_beam, cur_beam_size, batch_size, beam_size):
-        """state [B*cur_beam, ...] -> rows of the surviving beams [B*beam, ...]."""
-
-        def fn(tensor):
-            tail = [int(s) for s in tensor.shape[1:]]
-            index = selected_beam.view(batch_size, beam_size, *([1] * len(tail))).expand(batch_size, beam_size, *tail)
-            picked = torch.gather(tensor.view(batch_size, cur_beam_size, *tail), 1, index)
-            return picked.view(-1, *tail)
-
-        return fn
-
     def _kv_cached_modules(self):
         return [layer.self_att for layer in self.cap_generator.layers]
 
@@ -243,27 +310,17 @@ class Transformer(BaseCaptioner):
         cur_beam = 1 if timestep == 0 else beam_size
         word_logprob = self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)
         word_logprob = word_logprob.view(batch_size, cur_beam, -1)
-        V = word_logprob.shape[-1]
-        fused = _FUSED_BEAM_STEP and not return_probs and not kwargs and beam_ops.supported(word_logprob, cur_beam, beam_size)
-        if fused:
+        fused = None
+        if _FUSED_BEAM_STEP and not return_probs and not kwargs and beam_ops.supported(word_logprob, cur_beam, beam_size):
             # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py)
-            selected_beam, selected_words, seq_logprob, seq_mask, picked = beam_ops.beam_step(
-                word_logprob, self.seq_logprob, self.seq_mask if timestep > 0 else None,
-                self.selected_words if timestep > 0 else None, eos_idx, beam_size)
-        else:
-            candidates = self.seq_logprob + word_logprob
-            if timestep > 0:
-                alive = (self.selected_words.view(batch_size, cur_beam) != eos_idx).float().unsqueeze(-1)
-                self.seq_mask = self.seq_mask * alive
-                word_logprob = word_logprob * self.seq_mask
-                frozen = self.seq_logprob.expand_as(candidates).contiguous()
-                frozen[:, :, 1:] = -999  # a finished beam survives only through vocabulary index 0
-                candidates = self.seq_mask * candidates + frozen * (1 - self.seq_mask)
+            fused = beam_ops.beam_step(word_logprob, self.seq_logprob, self.seq_mask if timestep > 0 else None,
+                                       self.selected_words if timestep > 0 else None, eos_idx, beam_size)
+        outputs = self._beam_advance((self,), timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
+                                     eos_idx, **kwargs)
+        return samples, outputs
 
-            selected_idx, selected_logprob = self.select(timestep, candidates, beam_size, **kwargs)
-            selected_beam = torch.div(selected_idx, V, rounding_mode='floor')
-            selected_words = selected_idx - selected_beam * V
-
+    def _follow_beams(self, selected_beam, cur_beam, batch_size, beam_size):
+        """Re-gather the registered states by the surviving beams (reference transformer.py:229)."""
         expand = self._expand_state(selected_beam, cur_beam, batch_size, beam_size)
         # All beams of an image carry the SAME visual memory: re-gathering it by the surviving beam index (reference :229)
         # moves nothing, and replicating it per beam at step 0 only multiplies what every cross-attention reads.  The four
@@ -277,28 +334,3 @@ class Transformer(BaseCaptioner):
                 m._beam_src = selected_beam
                 visual.update((id(m.running_keys), id(m.running_values)))
         self.apply_to_states(lambda tensor: tensor if id(tensor) in visual else expand(tensor))
-
-        beam_col = selected_beam.unsqueeze(-1)
-        if fused:
-            self.seq_logprob, self.seq_mask = seq_logprob, seq_mask
-        else:
-            self.seq_logprob = selected_logprob.unsqueeze(-1)
-            self.seq_mask = torch.gather(self.seq_mask, 1, beam_col)
-        # the history of every surviving beam moves with it: ONE gather of the concatenated columns instead of one per past
-        # step (the lists hold a single [B, beam, t] tensor from step 1 on)
-        if outputs:
-            hist = outputs[0] if len(outputs) == 1 else torch.cat(outputs, -1)
-            outputs = [torch.gather(hist, 1, beam_col.expand(batch_size, beam_size, hist.shape[-1]))]
-        outputs.append(selected_words.unsqueeze(-1))
-        if return_probs:
-            lp = word_logprob.expand((batch_size, beam_size, -1)) if timestep == 0 else word_logprob
-            self.all_log_probs.append(lp.unsqueeze(2))
-        if not fused:
-            picked = torch.gather(word_logprob, 1, beam_col.expand(batch_size, beam_size, V))
-            picked = torch.gather(picked, 2, selected_words.unsqueeze(-1))
-        if self.log_probs:
-            hist = self.log_probs[0] if len(self.log_probs) == 1 else torch.cat(self.log_probs, -1)
-            self.log_probs = [torch.gather(hist, 1, beam_col.expand(batch_size, beam_size, hist.shape[-1]))]
-        self.log_probs.append(picked)
-        self.selected_words = selected_words.view(-1, 1)
-        return samples, outputs

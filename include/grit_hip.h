@@ -37,6 +37,8 @@
  *   grit_topk_rows_f32   <- Transformer.select (models/caption/transformer.py:184-188): sort of beam x vocabulary candidates
  *   grit_beam_step_f32   <- the body of Transformer.iter after the word log-probabilities (models/caption/transformer.py:208-240):
  *                           finished-beam masking, candidate scores, selection, beam / word split, score / mask / log-prob gathers
+ *   grit_beam_step_mean_f32 <- the same after the averaged word log-probabilities of an ensemble (models/caption/ensemble.py:128-214:
+ *                           torch.mean(torch.stack(per_model), 0) followed by the body of `iter`)
  *   grit_decode_step_inputs <- CaptionGenerator.get_seq_inputs in stateful mode + the word / position embedding sum
  *                           (models/caption/cap_generator.py:116-137,148)
  *   grit_kv_append       <- running_keys / running_values of the stateful self-attention (models/common/attention.py:166-181) and
@@ -55,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 43
+#define GRIT_ABI_VERSION 44
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -620,6 +622,22 @@ int grit_beam_step_f32(const float* logp, long ld, const float* seq_logprob, con
                        int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes,
                        int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The beam-search step of an ensemble of n_maps <= 8 captioners (reference models/caption/ensemble.py:128-214): grit_beam_step_f32
+ * applied to the average of n_maps word log-probability maps, each [B * cur_beam, V] float32 with the common row stride ld.
+ * maps is a HOST array of n_maps device pointers; they travel by value in the kernel arguments (no table to upload, nothing that
+ * a captured HIP graph has to keep alive).  The average is formed in registers while the candidates are scored -- it is never
+ * written -- and is bit-identical to torch.stack(maps).mean(0) on the device: per element, map m is added to accumulator m % 4
+ * (each starting at 0), the four are summed as ((a0 + a1) + a2) + a3 and multiplied by float(N) / float(n_maps * N), N =
+ * B * cur_beam * V.  picked_logprob is taken from that average.  Outputs, workspace (grit_beam_step_workspace), limits and the
+ * order of ties are those of grit_beam_step_f32; with n_maps == 1 every output equals grit_beam_step_f32's bit for bit.
+ * Two launches; safe to capture in a HIP graph.
+ * ------------------------------------------------------------------------------------------------------ */
+int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                            const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace,
+                            long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
+                            float* picked_logprob, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Gated merge of the grid / region cross-attentions of a caption decoder layer, inference only (reference

@@ -1,7 +1,10 @@
 """Single-image captioning (reference inference_caption.py:34-69): build detector + Transformer, optional checkpoint
 (`state_dict` key, strict=False), NestedTensor batch of one, beam search, token ids -> words through vocab.json.
 
-    python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth] [--vocab data/vocab.json] [--beam 5]
+    python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth [ckpt2.pth ...]] [--vocab data/vocab.json] [--beam 5]
+
+Several checkpoints: one model per checkpoint, captioned together by models.caption.ensemble.Ensemble (their word
+log-probabilities averaged at every beam step).
 
 `caption_tokens()` is the plumbing the tests drive (BASELINE config 1: 224x224, beam 1 = greedy, CPU with the
 oracle ops injected)."""
@@ -29,6 +32,15 @@ def build_model(config, device, checkpoint=''):
         print(f"model missing:{len(missing)} model unexpected:{len(unexpected)}")
     model.cached_features = False
     return model.eval()
+
+
+def build_captioner(config, device, checkpoints=('',)):
+    """One checkpoint: build_model.  Several: one model per checkpoint, in one Ensemble."""
+    checkpoints = list(checkpoints) or ['']
+    if len(checkpoints) == 1:
+        return build_model(config, device, checkpoints[0])
+    from models.caption.ensemble import Ensemble
+    return Ensemble([build_model(config, device, c) for c in checkpoints], bos_idx=config.model.bos_idx, config=config).eval()
 
 
 @torch.inference_mode()
@@ -78,7 +90,7 @@ def _caption_stream_device(model, batches, config, beam, device):
         try:
             with torch.cuda.stream(dec_stream):
                 dec_stream.wait_event(ready)
-                for v in vis.values():
+                for v in _feature_tensors(vis):
                     v.record_stream(dec_stream)
                 out = model(vis, seq=None, use_beam_search=True, max_len=config.model.beam_len,
                             eos_idx=config.model.eos_idx, beam_size=beam, out_size=1, return_probs=False)
@@ -103,7 +115,7 @@ def _caption_stream_device(model, batches, config, beam, device):
             if isinstance(tns, torch.Tensor) and tns.is_cuda:
                 tns.record_stream(det_stream)
         with torch.cuda.stream(det_stream):
-            vis = dict(model.detector(samples))
+            vis = _detect(model, samples)
             ready = torch.cuda.Event()
             ready.record(det_stream)
         if pending is not None:
@@ -111,6 +123,17 @@ def _caption_stream_device(model, batches, config, beam, device):
         pending = (vis, ready)
     if pending is not None:
         yield beam_search(*pending)
+
+
+def _detect(model, samples):
+    """Visual features of one batch: the detector's dict, or for an Ensemble one dict per member (each its own detector)."""
+    detect = getattr(model, 'detect', None)
+    return detect(samples) if detect is not None else dict(model.detector(samples))
+
+
+def _feature_tensors(vis):
+    for d in (vis if isinstance(vis, list) else [vis]):
+        yield from d.values()
 
 
 def decode(tokens, vocab_path, eos_idx=3):
@@ -132,13 +155,13 @@ def decode(tokens, vocab_path, eos_idx=3):
 def run_main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--img', required=True)
-    ap.add_argument('--checkpoint', default='')
+    ap.add_argument('--checkpoint', nargs='+', default=[''], help="one checkpoint, or several for an ensemble")
     ap.add_argument('--vocab', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'vocab.json'))
     ap.add_argument('--beam', type=int, default=None)
     a = ap.parse_args()
     config = default_config()
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
-    model = build_model(config, device, a.checkpoint)
+    model = build_captioner(config, device, a.checkpoint)
     if a.img.endswith('.npy'):
         import numpy as np
         image = torch.from_numpy(np.load(a.img)).float()
