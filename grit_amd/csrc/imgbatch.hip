@@ -250,3 +250,394 @@ extern "C" int grit_image_batch_fwd(const uint8_t* src, const int64_t* desc, con
                        tmp, d, tables, lut, out_h, out_w, out, mask);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// RandAugment between the resize and the float stage (reference datasets/caption/transforms/randaug.py:74-104), with
+// Pillow's arithmetic on the resized uint8 image: grit_image_batch_aug_fwd.  The vertical pass writes uint8 (dword-aligned
+// rows, like the intermediate), up to four stages run over two ping-pong buffers -- every image of the batch takes its
+// own operation of that stage from its descriptor row, one launch per stage -- and a last launch applies the lookup
+// table, the padding and the mask.  AutoContrast needs the per-channel min / max and Contrast the sum of the grey values
+// of the image as it stands before that stage: the launch that WRITES those bytes (the vertical pass or the stage
+// before) reduces them per block and the reader reduces the blocks' records: integers, so the order does not matter.
+// All byte streams: a stage reads and writes 3 * h * w bytes per image.
+namespace {
+
+constexpr int kAugHeader = 4;  // buf_off, op count, two spare
+constexpr int kAugStage = 8;   // op, seven parameters
+static_assert(kAugHeader + GRIT_IMAGE_AUG_STAGES * kAugStage == GRIT_IMAGE_AUG_FIELDS, "augmentation descriptor layout");
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t* v, int k) { return (v[k >> 2] >> (8 * (k & 3))) & 0xffu; }
+
+__device__ __forceinline__ uint32_t grey(uint32_t r, uint32_t g, uint32_t b) {  // Pillow's RGB -> L
+    return (r * 19595u + g * 38470u + b * 7471u + 0x8000u) >> 16;
+}
+
+// Every float expression below must round like Pillow's C / Python's doubles: one rounding per operation, never a fused
+// multiply-add.  The contraction pragma is what guarantees it (the __fmul_rn / __dadd_rn family are plain operators in
+// the HIP headers and would still be contracted), so it is stated again here, for the device code.
+#pragma clang fp contract(off)
+
+// Pillow's ImagingBlend(degenerate, image, alpha) on one byte: fp32 multiply, then fp32 add, each rounded
+__device__ __forceinline__ uint32_t blend8(uint32_t d, uint32_t i, float alpha) {
+    const float product = alpha * (float)((int)i - (int)d);
+    const float t = (float)d + product;
+    if (alpha >= 0.f && alpha <= 1.f) return (uint32_t)(int)t;  // between d and i
+    return t <= 0.f ? 0u : t >= 255.f ? 255u : (uint32_t)(int)t;
+}
+
+__device__ __forceinline__ uint32_t clip8f(float s) { return s <= 0.f ? 0u : s >= 255.f ? 255u : (uint32_t)(int)s; }
+
+// Statistics for AutoContrast (per-channel min / max) and Contrast (sum of the grey values), taken of the image as it
+// stands before that stage.  The launch that WRITES those bytes gathers them: every block reduces its own pixels and
+// stores one record of 8 words -- [0..2] 255 - min, [3..5] max per channel, [6..7] the 64-bit grey sum -- into its own
+// slot of stats[image][stage][block]; the stage that needs them reduces the image's records again.  Integers only, no
+// atomics, nothing to zero: a record is read only if the descriptor made every block of the writer store it.
+struct Stats {
+    uint32_t inv_lo[3], hi[3];
+    unsigned long long sum;
+};
+
+__device__ __forceinline__ bool needs_stats(int op) { return op == GRIT_AUG_AUTOCONTRAST || op == GRIT_AUG_CONTRAST; }
+
+// block-wide reduction (all 256 threads call it); every thread returns the block's result
+__device__ __forceinline__ Stats reduce_block(Stats s, uint32_t (*red)[8]) {
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            s.inv_lo[c] = max(s.inv_lo[c], (uint32_t)__shfl_xor((int)s.inv_lo[c], off, 64));
+            s.hi[c] = max(s.hi[c], (uint32_t)__shfl_xor((int)s.hi[c], off, 64));
+        }
+        s.sum += __shfl_xor(s.sum, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            red[wave][c] = s.inv_lo[c];
+            red[wave][3 + c] = s.hi[c];
+        }
+        red[wave][6] = (uint32_t)s.sum;
+        red[wave][7] = (uint32_t)(s.sum >> 32);
+    }
+    __syncthreads();
+    Stats r = {{0u, 0u, 0u}, {0u, 0u, 0u}, 0ull};
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            r.inv_lo[c] = max(r.inv_lo[c], red[w][c]);
+            r.hi[c] = max(r.hi[c], red[w][3 + c]);
+        }
+        r.sum += (unsigned long long)red[w][6] | (unsigned long long)red[w][7] << 32;
+    }
+    __syncthreads();  // red may be used again
+    return r;
+}
+
+// writer side: v = the thread's 4 pixels, n of them real; rec = this block's record
+__device__ __forceinline__ void write_stats(const uint32_t* v, int n, uint32_t* __restrict__ rec, uint32_t (*red)[8]) {
+    Stats s = {{0u, 0u, 0u}, {0u, 0u, 0u}, 0ull};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i >= n) continue;
+        const uint32_t px[3] = {byte_of(v, 3 * i), byte_of(v, 3 * i + 1), byte_of(v, 3 * i + 2)};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            s.inv_lo[c] = max(s.inv_lo[c], 255u - px[c]);
+            s.hi[c] = max(s.hi[c], px[c]);
+        }
+        s.sum += grey(px[0], px[1], px[2]);
+    }
+    s = reduce_block(s, red);
+    if (threadIdx.x == 0) {
+        reinterpret_cast<uint4*>(rec)[0] = make_uint4(s.inv_lo[0], s.inv_lo[1], s.inv_lo[2], s.hi[0]);
+        reinterpret_cast<uint4*>(rec)[1] = make_uint4(s.hi[1], s.hi[2], (uint32_t)s.sum, (uint32_t)(s.sum >> 32));
+    }
+}
+
+// reader side: the image's records -> its statistics, in every thread
+__device__ __forceinline__ Stats read_stats(const uint32_t* __restrict__ recs, int nblk, uint32_t (*red)[8]) {
+    Stats s = {{0u, 0u, 0u}, {0u, 0u, 0u}, 0ull};
+    for (int i = threadIdx.x; i < nblk; i += 256) {
+        const uint4 a = reinterpret_cast<const uint4*>(recs)[2 * i], b = reinterpret_cast<const uint4*>(recs)[2 * i + 1];
+        s.inv_lo[0] = max(s.inv_lo[0], a.x); s.inv_lo[1] = max(s.inv_lo[1], a.y); s.inv_lo[2] = max(s.inv_lo[2], a.z);
+        s.hi[0] = max(s.hi[0], a.w); s.hi[1] = max(s.hi[1], b.x); s.hi[2] = max(s.hi[2], b.y);
+        s.sum += (unsigned long long)b.z | (unsigned long long)b.w << 32;
+    }
+    return reduce_block(s, red);
+}
+
+// 4 pixels -> 3 dwords, zero past the row end; stores only the dwords that belong to the row
+__device__ __forceinline__ void store_quad(uint8_t* __restrict__ row, int px0, int pitch, const uint32_t* o) {
+    uint32_t* __restrict__ q = reinterpret_cast<uint32_t*>(row + 3 * px0);
+    const int words = min(3, (pitch - 3 * px0) >> 2);
+    q[0] = o[0];
+    if (words > 1) q[1] = o[1];
+    if (words > 2) q[2] = o[2];
+}
+
+__device__ __forceinline__ void load_quad(const uint8_t* __restrict__ row, int px0, int pitch, uint32_t* v) {
+    const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(row + 3 * px0);
+    const int words = min(3, (pitch - 3 * px0) >> 2);
+    v[0] = q[0];
+    v[1] = words > 1 ? q[1] : 0u;
+    v[2] = words > 2 ? q[2] : 0u;
+}
+
+// one thread per 4 pixels of one row; threads of a block run over the rows of the image (row-major quads)
+struct Quad { int yy, px0; bool active; };
+__device__ __forceinline__ Quad quad_of(int block, int h, int w) {
+    const int quads = (w + 3) >> 2;
+    const int t = block * 256 + threadIdx.x;
+    Quad q;
+    q.yy = t / quads;
+    q.px0 = 4 * (t - q.yy * quads);
+    q.active = q.yy < h;
+    return q;
+}
+
+// pass 2 of the augmented path: vertical taps -> uint8 rows of work buffer 0 (+ the statistics of the first operation)
+__global__ __launch_bounds__(256)
+void resample_cols_u8(const uint8_t* __restrict__ tmp, const ImageDesc* __restrict__ desc, const int32_t* __restrict__ tables,
+                      const int32_t* __restrict__ aug, uint8_t* __restrict__ work, uint32_t* __restrict__ stats) {
+    __shared__ uint32_t red[4][8];
+    const ImageDesc d = desc[blockIdx.z];
+    const int32_t* __restrict__ a = aug + (int64_t)blockIdx.z * GRIT_IMAGE_AUG_FIELDS;
+    // neighbouring rows share their source rows: one contiguous band of blocks per XCD (gridDim.x is a multiple of 8)
+    const int block = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const int oh = (int)d.dst_h, ow = (int)d.dst_w, pitch = tmp_pitch(ow);
+    const Quad q = quad_of(block, oh, ow);
+    uint32_t o[3] = {0u, 0u, 0u};
+    if (q.active) {
+        int s[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s[i] = 1 << (kPrecisionBits - 1);
+        const int first = tables[d.yb_off + 2 * q.yy], count = tables[d.yb_off + 2 * q.yy + 1];
+        const int32_t* __restrict__ k = tables + d.yt_off + (int64_t)q.yy * d.ky;
+        const uint8_t* __restrict__ p = tmp + d.tmp_off + (int64_t)first * pitch;
+        for (int y = 0; y < count; ++y) {
+            uint32_t v[3];
+            load_quad(p, q.px0, pitch, v);
+            const int t = k[y];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) s[i] += __mul24((int)byte_of(v, i), t);
+            p += pitch;
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            if (q.px0 + i / 3 < ow) o[i >> 2] |= (uint32_t)clip8(s[i]) << (8 * (i & 3));
+        store_quad(work + a[0] + (int64_t)q.yy * pitch, q.px0, pitch, o);
+    }
+    if (needs_stats(a[kAugHeader]))  // block-uniform
+        write_stats(o, q.active ? min(4, ow - q.px0) : 0,
+                    stats + (((int64_t)blockIdx.z * GRIT_IMAGE_AUG_STAGES) * gridDim.x + block) * 8, red);
+}
+
+// one 20-byte window of a row around the thread's 12 bytes (byte k of the quad = window byte 4 + k)
+__device__ __forceinline__ void load_window(const uint8_t* __restrict__ row, int px0, int pitch, uint32_t* win) {
+    load_quad(row, px0, pitch, win + 1);
+    const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(row + 3 * px0);
+    win[0] = px0 > 0 ? q[-1] : 0u;
+    win[4] = 3 * px0 + 16 <= pitch ? q[3] : 0u;
+}
+
+// one augmentation stage: in -> out for every image of the batch, each with its own operation (block-uniform)
+__global__ __launch_bounds__(256)
+void augment_stage(const ImageDesc* __restrict__ desc, const int32_t* __restrict__ aug, const int32_t* __restrict__ tables,
+                   const uint8_t* __restrict__ in, uint8_t* __restrict__ out, uint32_t* __restrict__ stats, int stage) {
+    __shared__ uint8_t lut[3 * 256];
+    __shared__ uint32_t red[4][8];
+    const ImageDesc d = desc[blockIdx.z];
+    const int32_t* __restrict__ a = aug + (int64_t)blockIdx.z * GRIT_IMAGE_AUG_FIELDS;
+    const int32_t* __restrict__ p = a + kAugHeader + stage * kAugStage;
+    const int n_ops = min(a[1], GRIT_IMAGE_AUG_STAGES);
+    if (stage >= n_ops) return;  // this image's plan is shorter (block-uniform): its result stays in buffer n_ops & 1
+    const int op = p[0];
+    const int next_op = stage + 1 < n_ops ? p[kAugStage] : GRIT_AUG_COPY;
+    const int h = (int)d.dst_h, w = (int)d.dst_w, pitch = tmp_pitch(w);
+    uint32_t* __restrict__ st = stats + ((int64_t)blockIdx.z * GRIT_IMAGE_AUG_STAGES + stage) * gridDim.x * 8;  // this stage's records
+    const uint8_t* __restrict__ src = in + a[0];
+    Stats stat = {{0u, 0u, 0u}, {0u, 0u, 0u}, 0ull};
+    if (needs_stats(op)) stat = read_stats(st, gridDim.x, red);  // block-uniform
+    if (op == GRIT_AUG_AUTOCONTRAST) {  // PIL.ImageOps.autocontrast: per channel a table from (lo, hi), fp64, separate roundings
+        for (int i = threadIdx.x; i < 3 * 256; i += 256) {
+            const int c = i >> 8, v = i & 255;
+            const int lo = 255 - (int)stat.inv_lo[c], hi = (int)stat.hi[c];
+            int r = v;
+            if (hi > lo) {
+                const double scale = 255.0 / (double)(hi - lo);
+                const double offset = (double)(-lo) * scale;
+                const double scaled = (double)v * scale;
+                r = (int)(scaled + offset);
+                r = min(max(r, 0), 255);
+            }
+            lut[i] = (uint8_t)r;
+        }
+        __syncthreads();
+    }
+    const Quad q = quad_of(blockIdx.x, h, w);
+    uint32_t b[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) b[i] = 0u;
+    if (q.active) {
+        const int yy = q.yy, px0 = q.px0;
+        const uint8_t* __restrict__ row = src + (int64_t)yy * pitch;
+        if (op == GRIT_AUG_AFFINE_FIXED || op == GRIT_AUG_AFFINE_TABLE) {  // nearest neighbour, fill 0
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int x = px0 + i;
+                int xin = -1, yin = -1;
+                if (x < w) {
+                    if (op == GRIT_AUG_AFFINE_FIXED) {  // 16.16 fixed point; wraps like the sums of Pillow's int walk
+                        xin = (int)((uint32_t)p[3] + (uint32_t)p[1] * (uint32_t)x + (uint32_t)p[2] * (uint32_t)yy) >> 16;
+                        yin = (int)((uint32_t)p[6] + (uint32_t)p[4] * (uint32_t)x + (uint32_t)p[5] * (uint32_t)yy) >> 16;
+                    } else {  // index tables walked in doubles on the host
+                        xin = tables[p[1] + x];
+                        yin = tables[p[2] + yy];
+                    }
+                }
+                if (xin >= 0 && xin < w && yin >= 0 && yin < h) {
+                    const uint8_t* __restrict__ s = src + (int64_t)yin * pitch + 3 * xin;
+                    b[3 * i] = s[0]; b[3 * i + 1] = s[1]; b[3 * i + 2] = s[2];
+                }
+            }
+        } else if (op == GRIT_AUG_SHARPNESS) {  // blend(3 x 3 SMOOTH, image): fp32, no contraction, Pillow's order of sums
+            const float alpha = __int_as_float(p[1]);
+            const float k1 = (float)(1.0 / 13.0), k5 = (float)(5.0 / 13.0);
+            uint32_t mid[5];
+            load_window(row, px0, pitch, mid);
+            const bool inner_row = h >= 3 && w >= 3 && yy > 0 && yy < h - 1;
+            uint32_t up[5] = {0u, 0u, 0u, 0u, 0u}, down[5] = {0u, 0u, 0u, 0u, 0u};  // rows yy - 1 and yy + 1
+            if (inner_row) {
+                load_window(row - pitch, px0, pitch, up);
+                load_window(row + pitch, px0, pitch, down);
+            }
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                const int x = px0 + k / 3;
+                const uint32_t centre = byte_of(mid, 4 + k);
+                uint32_t deg = centre;
+                if (inner_row && x > 0 && x < w - 1) {
+                    float s = 0.5f;
+                    s += ((float)byte_of(down, 1 + k) * k1 + (float)byte_of(down, 4 + k) * k1) + (float)byte_of(down, 7 + k) * k1;
+                    s += ((float)byte_of(mid, 1 + k) * k1 + (float)centre * k5) + (float)byte_of(mid, 7 + k) * k1;
+                    s += ((float)byte_of(up, 1 + k) * k1 + (float)byte_of(up, 4 + k) * k1) + (float)byte_of(up, 7 + k) * k1;
+                    deg = clip8f(s);
+                }
+                if (x < w) b[k] = blend8(deg, centre, alpha);
+            }
+        } else {  // point operations on the thread's own 12 bytes
+            uint32_t v[3];
+            load_quad(row, px0, pitch, v);
+            const float alpha = __int_as_float(p[1]);
+            uint32_t mean = 0u;
+            if (op == GRIT_AUG_CONTRAST) {  // int(sum / count + 0.5) of the grey image
+                const unsigned long long sum = stat.sum;
+                const unsigned long long count = (unsigned long long)h * (unsigned long long)w;
+                mean = (uint32_t)((2ull * sum + count) / (2ull * count));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (px0 + i >= w) continue;
+                const uint32_t r = byte_of(v, 3 * i), g = byte_of(v, 3 * i + 1), bl = byte_of(v, 3 * i + 2);
+                const uint32_t c3[3] = {r, g, bl};
+                const uint32_t l = grey(r, g, bl);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    uint32_t o = c3[c];  // GRIT_AUG_COPY
+                    if (op == GRIT_AUG_AUTOCONTRAST) o = lut[c * 256 + c3[c]];
+                    else if (op == GRIT_AUG_COLOR) o = blend8(l, c3[c], alpha);
+                    else if (op == GRIT_AUG_CONTRAST) o = blend8(mean, c3[c], alpha);
+                    else if (op == GRIT_AUG_BRIGHTNESS) o = blend8(0u, c3[c], alpha);
+                    b[3 * i + c] = o;
+                }
+            }
+        }
+    }
+    uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 12; ++i) o[i >> 2] |= b[i] << (8 * (i & 3));
+    if (q.active) store_quad(out + a[0] + (int64_t)q.yy * pitch, q.px0, pitch, o);
+    if (needs_stats(next_op))  // block-uniform
+        write_stats(o, q.active ? min(4, w - q.px0) : 0, st + ((int64_t)gridDim.x + blockIdx.x) * 8, red);
+}
+
+// last launch of the augmented path: uint8 rows (of the buffer each image ended in) -> lookup, one float4 store per colour plane, 4 mask bytes, zero padding
+__global__ __launch_bounds__(256)
+void normalize_pad(const uint8_t* __restrict__ work, long work_bytes, const ImageDesc* __restrict__ desc,
+                   const int32_t* __restrict__ aug, const float* __restrict__ lut, int out_h, int out_w,
+                   float* __restrict__ out, uint8_t* __restrict__ mask) {
+    __shared__ float table[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) table[i] = lut[i];
+    __syncthreads();
+    const ImageDesc d = desc[blockIdx.z];
+    const int yy = blockIdx.y;
+    const int px0 = 4 * (blockIdx.x * 256 + threadIdx.x);
+    if (px0 >= out_w) return;
+    const int ow = (int)d.dst_w, pitch = tmp_pitch(ow);
+    const bool inside = yy < d.dst_h && px0 < ow;
+    uint32_t v[3] = {0u, 0u, 0u};
+    if (inside) {  // an image with k operations ends in buffer k & 1
+        const int32_t* __restrict__ a = aug + (int64_t)blockIdx.z * GRIT_IMAGE_AUG_FIELDS;
+        load_quad(work + (min(a[1], GRIT_IMAGE_AUG_STAGES) & 1) * work_bytes + a[0] + (int64_t)yy * pitch, px0, pitch, v);
+    }
+    const int64_t plane = (int64_t)out_h * out_w;
+    float* __restrict__ o = out + (int64_t)blockIdx.z * 3 * plane + (int64_t)yy * out_w + px0;
+    uint8_t* __restrict__ m = mask + (int64_t)blockIdx.z * plane + (int64_t)yy * out_w + px0;
+    float f[3][4];
+    uint32_t pad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool real = inside && px0 + i < ow;
+        pad |= real ? 0u : 1u << (8 * i);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c][i] = real ? table[c * 256 + byte_of(v, 3 * i + c)] : 0.f;
+    }
+    if ((out_w & 3) == 0) {  // rows of the planes are 16-byte aligned
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(o + c * plane) = make_float4(f[c][0], f[c][1], f[c][2], f[c][3]);
+        *reinterpret_cast<uint32_t*>(m) = pad;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (px0 + i < out_w) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[c * plane + i] = f[c][i];
+                m[i] = (uint8_t)(pad >> (8 * i));
+            }
+    }
+}
+
+}  // namespace
+
+extern "C" int grit_image_batch_aug_fwd(const uint8_t* src, const int64_t* desc, const int32_t* tables, uint8_t* tmp,
+                                        const float* lut, const int32_t* aug, int n_stages, uint8_t* work, long work_bytes,
+                                        uint32_t* stats, int batch, int max_src_h, int max_dst_h, int max_dst_w, int max_kx,
+                                        int out_h, int out_w, float* out, uint8_t* mask, void* stream) {
+    if (!src || !desc || !tables || !tmp || !lut || !aug || !work || !stats || !out || !mask) return GRIT_ERR_BAD_ARG;
+    if (batch <= 0 || max_src_h <= 0 || max_dst_h <= 0 || max_dst_w <= 0 || max_kx <= 0 || out_h <= 0 || out_w <= 0 ||
+        max_dst_w > out_w || max_dst_h > out_h || n_stages < 0 || n_stages > GRIT_IMAGE_AUG_STAGES || work_bytes <= 0 || (work_bytes & 3))
+        return GRIT_ERR_BAD_ARG;
+    if (((uintptr_t)src | (uintptr_t)tmp | (uintptr_t)work) & 3 || (uintptr_t)stats & 15) return GRIT_ERR_BAD_ARG;
+    if (max_src_h > 65535 || out_h > 65535 || batch > 65535 || max_dst_h > 32767 || max_dst_w > 32767) return GRIT_ERR_UNSUPPORTED;
+    const ImageDesc* d = reinterpret_cast<const ImageDesc*>(desc);
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 pixels((max_dst_w + 255) / 256, (max_src_h + kRows - 1) / kRows, batch);
+    if (max_kx <= 7)
+        hipLaunchKernelGGL(resample_rows_k<7>, pixels, dim3(256), 0, s, src, d, tables, tmp);
+    else if (max_kx <= 9)
+        hipLaunchKernelGGL(resample_rows_k<9>, pixels, dim3(256), 0, s, src, d, tables, tmp);
+    else if (max_kx <= 13)
+        hipLaunchKernelGGL(resample_rows_k<13>, pixels, dim3(256), 0, s, src, d, tables, tmp);
+    else
+        hipLaunchKernelGGL(resample_rows_any, dim3((max_dst_w * 3 + 255) / 256, max_src_h, batch), dim3(256), 0, s,
+                           src, d, tables, tmp);
+    const int blocks = (int)GRIT_IMAGE_AUG_BLOCKS(max_dst_h, max_dst_w);  // the same grid for the writers and readers of `stats`
+    hipLaunchKernelGGL(resample_cols_u8, dim3(blocks, 1, batch), dim3(256), 0, s, tmp, d, tables, aug, work, stats);
+    for (int i = 0; i < n_stages; ++i)
+        hipLaunchKernelGGL(augment_stage, dim3(blocks, 1, batch), dim3(256), 0, s, d, aug, tables,
+                           work + (i & 1) * work_bytes, work + ((i + 1) & 1) * work_bytes, stats, i);
+    hipLaunchKernelGGL(normalize_pad, dim3((out_w + 1023) / 1024, out_h, batch), dim3(256), 0, s,
+                       work, work_bytes, d, aug, lut, out_h, out_w, out, mask);
+    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+}

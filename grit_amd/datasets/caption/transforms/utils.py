@@ -7,11 +7,12 @@ import numpy as np
 
 
 class Deferred(object):
-    """A decoded RGB image ([h, w, 3] uint8) waiting for the device-side resize to `size` = (newh, neww)."""
-    __slots__ = ('pixels', 'size')
+    """A decoded RGB image ([h, w, 3] uint8) waiting for the device-side resize to `size` = (newh, neww) and, when
+    `augment` is a plan of transforms/randaug.py, for the augmentation that follows the resize."""
+    __slots__ = ('pixels', 'size', 'augment')
 
-    def __init__(self, pixels, size):
-        self.pixels, self.size = pixels, size
+    def __init__(self, pixels, size, augment=None):
+        self.pixels, self.size, self.augment = pixels, size, augment
 
 
 def _pixels(x):

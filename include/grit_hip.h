@@ -32,6 +32,8 @@
  *                           (datasets/caption/transforms/utils.py:4-45), ToTensor + Normalize
  *                           (datasets/caption/transforms/__init__.py:6-32), zero padding + mask of
  *                           nested_tensor_from_tensor_list (engine/utils.py:278-295)
+ *   grit_image_batch_aug_fwd <- the same with RandAugment between the resize and ToTensor
+ *                           (datasets/caption/transforms/randaug.py:11-104: PIL transform / rotate / ImageOps / ImageEnhance)
  *   grit_gemm_bf16_nt    <- nn.Linear + nn.GELU of Mlp (models/common/swin_model.py:31-37) and their autograd backward:
  *                           fc1 + bias + exact GELU in one pass; fc2's input gradient x GELU' + fc1's bias gradient in one pass
  *   grit_topk_rows_f32   <- Transformer.select (models/caption/transformer.py:184-188): sort of beam x vocabulary candidates
@@ -57,7 +59,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 44
+#define GRIT_ABI_VERSION 45
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -523,6 +525,56 @@ int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bounds, int32
 int grit_image_batch_fwd(const uint8_t* src, const int64_t* desc, const int32_t* tables, uint8_t* tmp, const float* lut,
                          int batch, int max_src_h, int max_dst_w, int max_kx, int out_h, int out_w, float* out,
                          uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The same batch with RandAugment (datasets/caption/transforms/randaug.py:74-104) applied to every resized uint8 image
+ * before the lookup table, padding and mask; bit-identical to Pillow's transform(AFFINE) / rotate / ImageOps.autocontrast /
+ * ImageEnhance.{Color, Contrast, Brightness, Sharpness} chained on the host.  The random draws stay on the host: the
+ * caller passes what to do, per image and stage.
+ *
+ * grit_image_batch_aug_fwd (3 + n_stages launches: rows, columns -> uint8, one per stage, lookup + padding):
+ *   src, desc, tables, tmp, lut, out, mask, max_src_h, max_dst_w, max_kx, out_h, out_w   as for grit_image_batch_fwd
+ *   aug     [batch][GRIT_IMAGE_AUG_FIELDS] int32 (device):  [0] buf_off = byte offset (multiple of 4) of the image's slot in
+ *           each work buffer: dst_h rows of GRIT_IMAGE_TMP_PITCH(dst_w) bytes;  [1] k = number of operations of this image,
+ *           0 .. GRIT_IMAGE_AUG_STAGES: stages >= k leave the image alone and its result is read from work buffer k & 1;
+ *           [2], [3] zero;  then GRIT_IMAGE_AUG_STAGES records of 8: (op, p1 .. p7), zero (GRIT_AUG_COPY) from record k on.
+ *             GRIT_AUG_COPY          bytes unchanged
+ *             GRIT_AUG_AUTOCONTRAST  per channel lut[i] = clamp((int)(i * scale + offset)), scale = 255.0 / (hi - lo),
+ *                                    offset = -lo * scale in fp64 with separate roundings; unchanged where hi <= lo
+ *             GRIT_AUG_AFFINE_FIXED  p1..p6 = A0..A5, 16.16 fixed point (FIX(t) = floor(t * 65536 + 0.5); A2, A5 include the
+ *                                    half-pixel terms): xin = (A2 + A0 x + A1 y) >> 16, yin = (A5 + A3 x + A4 y) >> 16,
+ *                                    nearest neighbour, 0 outside.  Rotate and the shears with a non-zero off-diagonal term.
+ *             GRIT_AUG_AFFINE_TABLE  p1, p2 = offsets (int32 elements) inside `tables` of xin[dst_w] and yin[dst_h], built on
+ *                                    the host by Pillow's walk in doubles; entries outside [0, size) read as 0.  Translations.
+ *             GRIT_AUG_COLOR / _CONTRAST / _BRIGHTNESS / _SHARPNESS   p1 = the bits of the fp32 factor alpha;
+ *                                    out = blend(degenerate, image, alpha) per byte, t = (float)d + alpha * (float)(i - d) with an
+ *                                    fp32 multiply then an fp32 add; truncated for 0 <= alpha <= 1, else clamped to 0 / 255 first.
+ *                                    Degenerates: grey L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16; the constant
+ *                                    (2 * sum(L) + count) / (2 * count); zero; the 3 x 3 filter (1,1,1,1,5,1,1,1,1) / 13 in fp32
+ *                                    (border rows / columns and images below 3 x 3 unchanged).
+ *   n_stages  number of stage launches, 0 .. GRIT_IMAGE_AUG_STAGES: the largest k of the batch
+ *   work    uint8 scratch, 4-byte aligned: two buffers of work_bytes (multiple of 4) each, work_bytes >= sum of the slots
+ *   stats   uint32 [batch][GRIT_IMAGE_AUG_STAGES][GRIT_IMAGE_AUG_BLOCKS(max_dst_h, max_dst_w)][8] scratch, 16-byte aligned, not
+ *           initialised by the caller.  Per stage and block of 1024 pixels the statistics of that stage's INPUT, stored by
+ *           the launch that writes it and reduced by the stage that needs them (AutoContrast, Contrast): [0..2] 255 - min
+ *           and [3..5] max per channel, [6..7] the 64-bit sum of L.  Integers only, no atomics: deterministic
+ *   max_dst_h = max dst_h (<= out_h); dst_h, dst_w <= 32767
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_IMAGE_AUG_STAGES 4
+#define GRIT_IMAGE_AUG_FIELDS 36
+#define GRIT_IMAGE_AUG_BLOCKS(max_dst_h, max_dst_w) ((((long)(max_dst_h) * (((max_dst_w) + 3) / 4) + 255) / 256 + 7) / 8 * 8)
+#define GRIT_AUG_COPY 0
+#define GRIT_AUG_AUTOCONTRAST 1
+#define GRIT_AUG_AFFINE_FIXED 2
+#define GRIT_AUG_AFFINE_TABLE 3
+#define GRIT_AUG_COLOR 4
+#define GRIT_AUG_CONTRAST 5
+#define GRIT_AUG_BRIGHTNESS 6
+#define GRIT_AUG_SHARPNESS 7
+int grit_image_batch_aug_fwd(const uint8_t* src, const int64_t* desc, const int32_t* tables, uint8_t* tmp, const float* lut,
+                             const int32_t* aug, int n_stages, uint8_t* work, long work_bytes, uint32_t* stats, int batch,
+                             int max_src_h, int max_dst_h, int max_dst_w, int max_kx, int out_h, int out_w, float* out,
+                             uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogues (Swin Mlp, models/common/swin_model.py:31-37, on the [B*H*W, C] token maps).

@@ -1,8 +1,12 @@
 """Device image pipeline: time per batch (HIP events) and bytes moved, COCO-like sizes -> 384x640 (maxwh) or a fixed
-640x640 batch.  `python tools/bench_image_batch.py [--batch 32] [--iters 50]`"""
+640x640 batch.  `python tools/bench_image_batch.py [--batch 32] [--iters 50]`
+
+`--augment`: the RandAugment path instead -- batch of 480 x 640 sources -> (384, 512), `image_batch` with and without
+plans (drawn once with a fixed seed), same process, alternating rounds, HIP-event time per batch, launches and bytes."""
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -10,15 +14,62 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from grit_amd.datasets.caption.transforms import MaxWHResize  # noqa: E402
-from grit_amd.ops.image_batch import image_batch  # noqa: E402
+from grit_amd.datasets.caption.transforms import MaxWHResize, RandAugment  # noqa: E402
+from grit_amd.ops.image_batch import image_batch, plan_augment, tmp_pitch  # noqa: E402
+
+
+def timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, (time.perf_counter() - t0) / iters * 1e3
+
+
+def augmented(a):
+    rng = np.random.default_rng(0)
+    shapes, sizes = [(480, 640)] * a.batch, [(384, 512)] * a.batch
+    host = [torch.from_numpy(rng.integers(0, 256, s + (3,), dtype=np.uint8)) for s in shapes]
+    dev = [h.cuda() for h in host]
+    random.seed(0)
+    draw = RandAugment()
+    plans = [draw.draw() for _ in shapes]
+    _, _, n_stages, work = plan_augment(sizes, plans)
+    src = sum(3 * h * w for h, w in shapes)
+    tmp = sum(h * tmp_pitch(s[1]) for (h, w), s in zip(shapes, sizes))
+    out = a.batch * 384 * 512 * 13
+    plain_bytes = src + 2 * tmp + out  # rows: src -> tmp; columns: tmp -> floats + mask
+    aug_bytes = src + 2 * tmp + 2 * work + 2 * n_stages * work + out  # columns -> uint8, n stages, uint8 -> floats + mask
+    for feed, label in ((dev, 'device-resident'), (host, 'host, pageable (staged)')):
+        runs = {'plain': lambda: image_batch(feed, sizes, device='cuda'),
+                'augmented': lambda: image_batch(feed, sizes, device='cuda', augment=plans)}
+        for fn in runs.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        best = {k: (float('inf'), float('inf')) for k in runs}
+        for _ in range(a.rounds):  # alternate, keep the fastest round of each
+            for k, fn in runs.items():
+                best[k] = min(best[k], timed(fn, a.iters))
+        for k, nbytes, launches in (('plain', plain_bytes, 2), ('augmented', aug_bytes, 3 + n_stages)):
+            print(json.dumps({'case': '480x640->(384,512) ' + k, 'input': label, 'batch': a.batch, 'launches': launches,
+                              'ms_per_batch': round(best[k][0], 3),
+                              'wall_ms_per_batch': round(best[k][1], 3), 'moved_MB': round(nbytes / 1e6, 1),
+                              'GB_per_s': round(nbytes / best[k][0] / 1e6, 1)}))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--iters', type=int, default=50)
+    ap.add_argument('--augment', action='store_true', help="time the RandAugment path next to the plain one")
+    ap.add_argument('--rounds', type=int, default=5, help="alternating rounds of --iters batches each (--augment)")
     a = ap.parse_args()
+    if a.augment:
+        return augmented(a)
     rng = np.random.default_rng(0)
     coco = [(480, 640), (427, 640), (640, 480), (333, 500), (375, 500), (500, 375), (640, 428), (480, 640)]
     for name, shapes, policy in (('coco->maxwh(384,640)', [coco[i % 8] for i in range(a.batch)], MaxWHResize((384, 640))),
