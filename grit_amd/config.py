@@ -47,7 +47,8 @@ _DEFAULTS = {
     'optimizer': dict(warmup_init_lr=1e-5, min_lr=1e-4, xe_lr=1e-4, sc_lr=5e-6, xe_backbone_lr=1e-5,
                       sc_backbone_lr=5e-6, weight_decay=0.01, beta_1=0.9, beta_2=0.99, batch_size=16, num_workers=2,
                       freezing_xe_epochs=0, freezing_sc_epochs=0, finetune_xe_epochs=10, finetune_sc_epochs=10,
-                      freeze_detector=False, freeze_backbone=False),
+                      freeze_detector=False, freeze_backbone=False,
+                      sc_reward='host'),  # 'device': CIDEr-D of the beams in one kernel launch (grit_amd/ops/cider.py), no host round trip
 }
 
 

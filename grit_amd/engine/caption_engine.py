@@ -311,14 +311,21 @@ def train_sc_step(model, batch, optimizers, reward_fn, config):
     return gather_result(loss.detach()), gather_result(reward.mean()), gather_result(baseline.mean())
 
 
-def cider_reward_fn(cider, text_field, tokenizer_pool=None, tokenize=None):
+def cider_reward_fn(cider, text_field, tokenizer_pool=None, tokenize=None, reward='host'):
     """The reference's reward (:433-438): text_field.decode -> PTB tokenisation of generated and ground-truth captions ->
     cider.compute_score(...)[1].  `tokenize` defaults to the native PTB-style tokenizer
     (grit_amd.datasets.caption.metrics.PTBTokenizer.tokenize; the reference's is a Java program); with a `tokenizer_pool` the
-    two corpora are tokenised through pool.map as the reference does."""
+    two corpora are tokenised through pool.map as the reference does.
+    reward='device': the same numbers from one kernel launch on the tokens where they are (grit_amd/ops/cider.py); the
+    references of an image are tokenised and cooked when it is first seen, and the returned [B, beam] tensor stays on the device."""
     import itertools
 
     import numpy as np
+
+    if reward == 'device':
+        return _device_cider_reward_fn(cider, text_field, tokenize)
+    if reward != 'host':
+        raise ValueError("reward must be 'host' or 'device', not %r" % (reward,))
 
     if tokenize is None:
         from grit_amd.datasets.caption.metrics import PTBTokenizer
@@ -336,12 +343,39 @@ def cider_reward_fn(cider, text_field, tokenizer_pool=None, tokenize=None):
     return reward_fn
 
 
+def _device_cider_reward_fn(cider, text_field, tokenize):
+    if tokenize is not None:
+        raise ValueError("reward='device' scores with tables built from the native tokenizer: it takes no custom `tokenize`")
+    if getattr(cider, 'doc_frequency', None) is None:
+        raise ValueError("reward='device' needs a Cider built with corpus statistics (Cider(gts))")
+    vocab = getattr(text_field, 'vocab', None)
+    itos = vocab.itos if vocab is not None and hasattr(vocab, 'itos') else text_field.itos
+    eos_token = getattr(text_field, 'eos_token', '<eos>')
+    # the tables and the cooked references outlive this reward_fn (train_sc makes one per epoch): they are kept on the Cider
+    holder = cider.__dict__.setdefault('_device_scorers', {})
+    vocab_key = (eos_token, hash(tuple(itos)))
+
+    def reward_fn(tokens, batch):
+        from grit_amd import lib
+        from grit_amd.ops.cider import DeviceCider
+        lib.require_device(tokens)
+        scorer = holder.get((tokens.device, vocab_key))
+        if scorer is None:  # the tables live on the device the tokens come from; built at the first step
+            scorer = holder[(tokens.device, vocab_key)] = DeviceCider(cider, itos, eos_token=eos_token, device=tokens.device)
+        return scorer.reward(tokens, batch['captions'])
+
+    return reward_fn
+
+
 def train_sc(model, dataloaders, optimizers, cider, text_field, tokenizer_pool, device, epoch, config, rank=0, writer=None,
-             tokenize=None, evaluate=True, checkpoint=True):
+             tokenize=None, evaluate=True, checkpoint=True, reward=None):
     """Self-critical epoch (reference engine/caption_engine.py:388-492), same signature plus `tokenize` (the reference
-    hard-wires metrics.PTBTokenizer.tokenize, a Java program that is not part of this build)."""
+    hard-wires metrics.PTBTokenizer.tokenize, a Java program that is not part of this build) and `reward` ('host' / 'device',
+    default config.optimizer.sc_reward)."""
     model.train()
-    reward_fn = cider_reward_fn(cider, text_field, tokenizer_pool, tokenize)
+    if reward is None:
+        reward = getattr(getattr(config, 'optimizer', None), 'sc_reward', 'host')
+    reward_fn = cider_reward_fn(cider, text_field, tokenizer_pool, tokenize, reward=reward)
     running_loss = running_reward = running_baseline = 0.0
     n = len(dataloaders['train_dict'])
     for it, batch in enumerate(_progress(dataloaders['train_dict'], desc=f'Epoch {epoch} - train', unit='it')):

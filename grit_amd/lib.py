@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgrit_hip.so")
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 _c = ctypes
 _ptr, _int, _i64, _f32, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -96,6 +96,7 @@ SIGNATURES = {
     "grit_gemm_bf16_nt_res": [_ptr, _c.c_long] * 3 + [_int] * 3 + [_ptr, _ptr, _c.c_long, _ptr, _int, _ptr],
     "grit_gemm_bf16_nt_relu": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _c.c_float, _ptr, _ptr],
     "grit_gemm_bf16_nt_rows": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _ptr, _ptr, _int, _int, _ptr],
+    "grit_cider_reward": [_ptr, _int, _int, _ptr, _int, _ptr, _ptr, _ptr, _ptr],
 }
 
 SLAB_GROUP_MAX = 48  # GRIT_SLAB_GROUP_MAX
@@ -133,6 +134,19 @@ class RelbiasBwdJob(_c.Structure):
 
 
 RELBIAS_GROUP_MAX = 32  # GRIT_RELBIAS_GROUP_MAX
+
+
+class CiderTables(_c.Structure):
+    """grit_cider_tables of include/grit_hip.h."""
+    _fields_ = [("expansion", _c.c_void_p), ("word_meta", _c.c_void_p), ("vocab", _c.c_int), ("width", _c.c_int),
+                ("idf_key", _c.c_void_p), ("idf_val", _c.c_void_p), ("idf_start", _c.c_long * 5), ("slot_ref_start", _c.c_void_p),
+                ("n_slots", _c.c_int), ("ref_ent_start", _c.c_void_p), ("ent_tok", _c.c_void_p), ("ent_w", _c.c_void_p),
+                ("ref_norm", _c.c_void_p), ("ref_len", _c.c_void_p), ("sigma", _c.c_double), ("log_corpus", _c.c_double)]
+
+
+CIDER_MAX_TOKENS = 256  # GRIT_CIDER_MAX_TOKENS
+CIDER_MAX_EXPANSION = 8  # GRIT_CIDER_MAX_EXPANSION
+CIDER_META_FIN_SHIFT, CIDER_META_BLANK, CIDER_META_EOS = 4, 256, 512
 
 
 class TransposeJob(_c.Structure):

@@ -48,7 +48,9 @@
  *   grit_gate_pack, grit_gate_fuse
  *                        <- the sigmoid-gated merge of the two cross-attentions at inference, ParallelAttentionLayer.forward
  *                           (models/caption/cap_generator.py:44-56): masks, concatenations, sigmoids, products, sum, scale
- * (none of the last twelve groups has a native ancestor in the reference: they replace chains of torch / PIL ops)
+ *   grit_cider_reward    <- the self-critical reward, engine/caption_engine.py:433-438 (text_field.decode, PTBTokenizer.tokenize,
+ *                           cider.compute_score) and datasets/caption/metrics/cider/cider_scorer.py (counts2vec, sim, compute_cider)
+ * (none of the last thirteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops)
  */
 #ifndef GRIT_HIP_H
 #define GRIT_HIP_H
@@ -59,7 +61,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 45
+#define GRIT_ABI_VERSION 46
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -763,6 +765,54 @@ int grit_kv_append(const void* old_k, const void* old_v, const int64_t* src_beam
 int grit_decode_step_inputs(const int64_t* tokens, int64_t pad_idx, const void* word_emb, int vocab, const void* pos_emb, int n_pos,
                             int d, int is_bf16, int64_t* running_seq, const uint8_t* old_mask, int t_old, int rows, void* x,
                             void* mask_pad, uint8_t* new_mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * CIDEr-D reward of self-critical training (reference engine/caption_engine.py:433-438: decode the beams up to <eos>, PTB-tokenise,
+ * score against the image's ground-truth captions; datasets/caption/metrics/cider/cider_scorer.py: tf-idf vectors of the 1..4-grams,
+ * clipped cosine similarity, Gaussian length penalty exp(-(len_h - len_r)^2 / (2 sigma^2)), mean over orders and references, x 10).
+ * One launch, one workgroup per hypothesis row, float64 arithmetic with every sum in the host's order and no atomics: two launches
+ * on the same input are bit-identical.
+ *
+ * tokens [rows, T] int64, contiguous; rows = images * beam; slots [rows / beam] int32 = the reference slot of each image;
+ * out32 [rows] float32; out64 [rows] float64 or NULL.  An empty hypothesis scores 0.  A word id outside [0, vocab) in front of the
+ * first <eos>, or a slot outside [0, n_slots), gives NaN for that row (the host path raises there).
+ * T * width > GRIT_CIDER_MAX_TOKENS or width > GRIT_CIDER_MAX_EXPANSION: GRIT_ERR_UNSUPPORTED.  Any number of references per image.
+ * The tables are built by grit_amd/ops/cider.py (DeviceCider); every pointer is device memory:
+ *   expansion [vocab, 2, width] int32   tokens of a word anywhere in the caption ([w][0]) and as its last non-blank word ([w][1])
+ *   word_meta [vocab] int32             bits 0-3 count of [w][0], bits 4-7 count of [w][1], GRIT_CIDER_META_BLANK (whitespace-only
+ *                                       word), GRIT_CIDER_META_EOS (ends the row)
+ *   idf_key / idf_val                   the corpus n-grams as a trie flattened order by order: idf_key[idf_start[k] .. idf_start[k+1])
+ *                                       sorted keys (index of the (k)-gram prefix within order k-1, 0 for k = 0) << 32 | token of the
+ *                                       (k+1)-grams; idf_val = log(corpus size) - log(max(1, document frequency)) of the same entry.
+ *                                       An absent n-gram has idf = log_corpus.
+ *   slot_ref_start [n_slots + 1]        references of a slot, CSR
+ *   ref_ent_start [4 * n_refs + 1]      entries of (reference, order), CSR; ent_tok [entries] int4 = the n-gram's tokens padded with
+ *                                       -1 (16-byte aligned); ent_w [entries] its tf-idf weight; ref_norm [n_refs, 4]; ref_len [n_refs]
+ *                                       (length in bigram occurrences)
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_CIDER_MAX_TOKENS 256
+#define GRIT_CIDER_MAX_EXPANSION 8
+#define GRIT_CIDER_META_FIN_SHIFT 4
+#define GRIT_CIDER_META_BLANK 256
+#define GRIT_CIDER_META_EOS 512
+typedef struct {
+    const int32_t* expansion;
+    const int32_t* word_meta;
+    int vocab, width;
+    const uint64_t* idf_key;
+    const double* idf_val;
+    long idf_start[5];
+    const int32_t* slot_ref_start;
+    int n_slots;
+    const int32_t* ref_ent_start;
+    const void* ent_tok;
+    const double* ent_w;
+    const double* ref_norm;
+    const int32_t* ref_len;
+    double sigma, log_corpus;
+} grit_cider_tables;
+int grit_cider_reward(const int64_t* tokens, int rows, int T, const int32_t* slots, int beam, const grit_cider_tables* tab,
+                      float* out32, double* out64, void* stream);
 
 #ifdef __cplusplus
 }
