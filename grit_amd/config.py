@@ -33,7 +33,8 @@ def to_config(obj):
 
 
 _DEFAULTS = {
-    'exp': dict(seed=42, name='eval', rank=0, ngpus_per_node=8, world_size=8, checkpoint='', eval=False, resume=False),
+    'exp': dict(seed=42, name='eval', rank=0, ngpus_per_node=8, world_size=8, checkpoint='', eval=False, resume=False,
+                eval_scorer='device'),  # the per-epoch BLEU / ROUGE / CIDEr of train_caption.main: 'device' scores the beam tokens in one kernel launch (grit_amd/ops/caption_scores.py), 'host' decodes and scores in Python as the reference does (the choice for a run without a GPU: 'device' is refused there)
     'dataset': dict(overfit=False, ann_root='', img_root='', hdf5_path='', vocab_path='',
                     use_gri_feat=True, use_reg_feat=True,
                     transform_cfg=dict(size=[384, 640], resize_name='maxwh', randaug=False)),  # reference yaml: randaug true (host-side PIL); 'device' runs the same operations on the GPU

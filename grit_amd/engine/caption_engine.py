@@ -241,15 +241,56 @@ def train_xe(model, dataloaders, optimizers, text_field, epoch, rank=0, config=N
     return {'loss': running / max(1, n), 'reward': 0, 'reward_baseline': 0, 'val_loss': val_loss}
 
 
+def _host_scorer(gts, gen):
+    """The reference's scoring (engine/caption_engine.py:205-207): PTB-tokenise both sides, metrics.compute_scores."""
+    from grit_amd.datasets.caption import metrics
+    return metrics.compute_scores(metrics.PTBTokenizer.tokenize(gts), metrics.PTBTokenizer.tokenize(gen))[0]
+
+
+def _split_scorer(dataloader, caption_lists, text_field, device):
+    """The DeviceCaptionScorer of a split: built at its first evaluation, kept on the dataloader object (or, where that takes no
+    attribute, in a module table) and reused while the split's references are the same -- from the second epoch on a split costs
+    one launch and no tokenisation."""
+    from grit_amd.ops.caption_scores import DeviceCaptionScorer
+    vocab = getattr(text_field, 'vocab', None)
+    itos = vocab.itos if vocab is not None and hasattr(vocab, 'itos') else text_field.itos
+    eos_token = getattr(text_field, 'eos_token', '<eos>')
+    key = (tuple(tuple(c) for c in caption_lists), eos_token, hash(tuple(itos)), str(device))
+    own = getattr(dataloader, '__dict__', None)  # (a plain list of batches takes no attribute)
+    cache = own.setdefault('_grit_caption_scorers', {}) if own is not None else _SPLIT_SCORERS
+    scorer = cache.get(key)
+    if scorer is None:
+        while len(cache) >= (1 if own is not None else 4):  # a loader keeps one, the module table the last few splits
+            cache.pop(next(iter(cache)))
+        scorer = cache[key] = DeviceCaptionScorer(caption_lists, itos, eos_token=eos_token, device=device)
+    return scorer
+
+
+_SPLIT_SCORERS = {}
+
+
 def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='test', config=None, train_res=None,
-                     writer=None, best_cider=None, which='ft_xe', scheduler=None, log_and_save=True, scorer=None):
-    """Beam-search every batch (reference :165-183) and hand tokens to `scorer(gts, gen) -> dict` if given.
-    Returns (token tensors per batch, seconds per batch) when no scorer is supplied.  `model` may be an Ensemble
-    (models/caption/ensemble.py); it cannot save a best checkpoint, so with one best_cider must be None (or log_and_save False)."""
+                     writer=None, best_cider=None, which='ft_xe', scheduler=None, log_and_save=True, scorer=None, scores_out=None):
+    """Beam-search every batch (reference :165-183) and score the captions (:194-207).
+    scorer: None -- no scoring, returns (token tensors per batch, seconds per batch);
+            a callable `scorer(gts, gen) -> dict` on the collapsed, joined, untokenised captions;
+            'host' -- the reference's flow: decode, collapse repeated words, PTBTokenizer.tokenize, metrics.compute_scores;
+            'device' -- the same scores with the tokens left where beam search wrote them: the references are collected during the
+            loop, one launch of grit_caption_scores and one copy back at the end (grit_amd/ops/caption_scores.py).
+    The scores dictionary has the keys 'BLEU' (a list of four), 'ROUGE' and 'CIDEr'; the reference's METEOR is not computed.
+    With `best_cider` (and log_and_save) the best checkpoint is written when CIDEr >= best_cider and the CIDEr is returned;
+    a dictionary passed as `scores_out` receives the scores in either case.
+    `model` may be an Ensemble (models/caption/ensemble.py); it cannot save a best checkpoint, so with one best_cider must be
+    None (or log_and_save False)."""
+    if isinstance(scorer, str) and scorer not in ('host', 'device'):
+        raise ValueError("scorer must be None, a callable, 'host' or 'device', not %r" % (scorer,))
+    if isinstance(scorer, str) and text_field is None:
+        raise ValueError("scorer=%r needs a text_field" % (scorer,))
     if log_and_save and best_cider is not None:
         _refuse_ensemble_checkpoint(model)  # before the evaluation, not after it
     model.eval()
-    times, tokens, gen, gts = [], [], {}, {}
+    on_device = scorer == 'device'
+    times, tokens, gen, gts, caption_lists = [], [], {}, {}, []
     for it, batch in enumerate(_progress(dataloader, desc=f'Epoch {epoch} - evaluation on {split}', unit='it')):
         t0 = time.time()
         with torch.no_grad():
@@ -260,7 +301,9 @@ def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='
             torch.cuda.synchronize()
         times.append(time.time() - t0)
         tokens.append(out)
-        if text_field is not None and scorer is not None:
+        if on_device:
+            caption_lists.extend(batch['captions'])
+        elif text_field is not None and scorer is not None:
             import itertools
             for i, (gts_i, gen_i) in enumerate(zip(batch['captions'], text_field.decode(out, join_words=False))):
                 gen[f'{it}_{i}'] = [' '.join(k for k, _ in itertools.groupby(gen_i))]
@@ -268,7 +311,21 @@ def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='
     avg = sum(times) / max(1, len(times))
     if scorer is None:
         return tokens, avg
-    scores = scorer(gts, gen)
+    if on_device:
+        device_scorer = _split_scorer(dataloader, caption_lists, text_field, tokens[0].device)
+        T = max(o.shape[-1] for o in tokens)
+        if any(o.shape[-1] != T for o in tokens):  # a batch that ended early is padded with the id the scorer cuts at
+            if device_scorer.eos_id is None:
+                raise ValueError("batches of different lengths cannot be padded: %r is not in the vocabulary" % (device_scorer.tables.eos_token,))
+            tokens_ = [torch.nn.functional.pad(o.reshape(-1, o.shape[-1]), (0, T - o.shape[-1]), value=device_scorer.eos_id) for o in tokens]
+        else:
+            tokens_ = [o.reshape(-1, T) for o in tokens]
+        rows = torch.cat(tokens_)
+        scores = device_scorer.aggregate(*device_scorer.launch(rows))
+    else:
+        scores = (_host_scorer if scorer == 'host' else scorer)(gts, gen)
+    if scores_out is not None:
+        scores_out.update(scores)
     if log_and_save and best_cider is not None and scores.get('CIDEr', 0) >= best_cider:
         best = (scores['CIDEr'], 0) if split == 'valid' else (0, scores['CIDEr'])
         save_checkpoint(model, optimizers=optimizers, epoch=epoch, scores=scores, best_ciders=best, config=config,

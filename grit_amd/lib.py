@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgrit_hip.so")
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 _c = ctypes
 _ptr, _int, _i64, _f32, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -97,6 +97,7 @@ SIGNATURES = {
     "grit_gemm_bf16_nt_relu": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _c.c_float, _ptr, _ptr],
     "grit_gemm_bf16_nt_rows": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _ptr, _ptr, _int, _int, _ptr],
     "grit_cider_reward": [_ptr, _int, _int, _ptr, _int, _ptr, _ptr, _ptr, _ptr],
+    "grit_caption_scores": [_ptr, _int, _int, _ptr, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
 }
 
 SLAB_GROUP_MAX = 48  # GRIT_SLAB_GROUP_MAX
@@ -144,6 +145,13 @@ class CiderTables(_c.Structure):
                 ("ref_norm", _c.c_void_p), ("ref_len", _c.c_void_p), ("sigma", _c.c_double), ("log_corpus", _c.c_double)]
 
 
+class ScoreTables(_c.Structure):
+    """grit_score_tables of include/grit_hip.h."""
+    _fields_ = [("ent_tf", _c.c_void_p), ("ref_words", _c.c_void_p), ("seq_start", _c.c_void_p), ("seq_tok", _c.c_void_p),
+                ("empty_tok", _c.c_int), ("beta2", _c.c_double)]
+
+
+SCORE_COMPONENTS = 10  # GRIT_SCORE_COMPONENTS
 CIDER_MAX_TOKENS = 256  # GRIT_CIDER_MAX_TOKENS
 CIDER_MAX_EXPANSION = 8  # GRIT_CIDER_MAX_EXPANSION
 CIDER_META_FIN_SHIFT, CIDER_META_BLANK, CIDER_META_EOS = 4, 256, 512

@@ -16,6 +16,10 @@ Layout (all built here, read by grit_amd/csrc/cider.hip):
   * the references of every image seen so far, cooked once by `Cider.cook`, CSR by slot / reference / order: token tuples
     padded to 4 with -1, tf-idf weights, the four norms and the length.  They are matched by token tuple, so a reference
     n-gram outside the corpus statistics still meets the same n-gram of a hypothesis.
+
+With `score_tables=True` (the evaluation's scorer, grit_amd/ops/caption_scores.py) every reference additionally leaves what BLEU
+and ROUGE-L need, in arrays beside the ones above (the layout grit_cider_reward reads is untouched): the raw term frequency next to
+each `ent_tok` entry, the word count, and the token sequence split at single spaces (CSR; the empty string is ONE empty token).
 """
 import ctypes
 import math
@@ -25,6 +29,7 @@ import numpy as np
 import torch
 
 from grit_amd import lib as _lib
+from grit_amd.datasets.caption.metrics import cider as _cider
 from grit_amd.datasets.caption.metrics import tokenizer as _tokenizer
 
 E = _lib.CIDER_MAX_EXPANSION
@@ -81,7 +86,7 @@ class DeviceCider(object):
     ids whose word equals `eos_token` end a row, as in the reference's TextField.decode.  `device` may be the CPU: the tables
     are then only packed (tests walk them), `reward` needs a HIP device."""
 
-    def __init__(self, cider, itos, eos_token='<eos>', device='cuda', verbose=False):
+    def __init__(self, cider, itos, eos_token='<eos>', device='cuda', verbose=False, score_tables=False):
         if getattr(cider, 'doc_frequency', None) is None or cider.ref_len is None:
             raise ValueError("DeviceCider needs a Cider built with corpus statistics (Cider(gts)); the call-local form is host-only")
         if cider._n != 4:
@@ -107,6 +112,13 @@ class DeviceCider(object):
         self.ref_len = _Grow(torch.int32, dev)
         self._n_ent = 0
         self._tables = None
+        self.score_tables = bool(score_tables)
+        if self.score_tables:
+            self.ent_tf = _Grow(torch.int32, dev)
+            self.ref_words = _Grow(torch.int32, dev)
+            self.seq_start = _Grow(torch.int32, dev, first=[0])
+            self.seq_tok = _Grow(torch.int32, dev)
+            self._n_seq = 0
         self.stats = {'vocab': len(self.itos), 'expansion_bytes': int(self.expansion.numel() * 4 + self.word_meta.numel() * 4),
                       'idf_entries': [int(b - a) for a, b in zip(self.idf_start[:-1], self.idf_start[1:])],
                       'idf_bytes': int(self.idf_key.numel() * 16), 'tokens': len(self._tok),
@@ -211,20 +223,23 @@ class DeviceCider(object):
         self.idf_val = torch.from_numpy(np.concatenate([allv, np.zeros(pad, np.float64)])).to(self.device)
 
     # ---- references ------------------------------------------------------------------------------------------------------
-    def reference_slots(self, captions):
+    def reference_slots(self, captions, sentences=None):
         """One slot per image of `captions` (a list of caption lists, batch['captions']).  An image seen before costs one
-        dictionary lookup; a new one is tokenised and cooked on the host, once, and appended to the device arrays."""
-        slots, new = [], {}
-        for caps in captions:
+        dictionary lookup; a new one is tokenised and cooked on the host, once, and appended to the device arrays.
+        `sentences`: the captions of every image already tokenised (PTBTokenizer.tokenize), for a caller that has them."""
+        slots, new, given = [], {}, {}
+        for i, caps in enumerate(captions):
             key = tuple(caps)
             s = self._slots.get(key)
             if s is None:
                 s = new.get(key)
                 if s is None:
                     s = new[key] = len(self._slots) + len(new)
+                    if sentences is not None:
+                        given[key] = sentences[i]
             slots.append(s)
         if new:
-            self._cook(list(new))  # (in slot order; nothing is registered if cooking raises)
+            self._cook(list(new), given)  # (in slot order; nothing is registered if cooking raises)
             self._slots.update(new)
         return slots
 
@@ -232,20 +247,30 @@ class DeviceCider(object):
         for caps in caption_lists:
             self.reference_slots([caps])
 
-    def _cook(self, images):
+    def _cook(self, images, tokenised=None):
         tid = self._tid
         ent_tok, ent_w, ent_start, norms, lens, ref_start = [], [], [], [], [], []
+        ent_tf, words, seq_tok, seq_start = [], [], [], []
         n_ref = self.ref_len.n
         for caps in images:
-            sentences = _tokenizer.PTBTokenizer.tokenize([list(caps)])[0] if caps else []
-            for vec in self.cider.cook(sentences):
+            sentences = tokenised.get(tuple(caps)) if tokenised else None
+            if sentences is None:
+                sentences = _tokenizer.PTBTokenizer.tokenize([list(caps)])[0] if caps else []
+            for sentence, vec in zip(sentences, self.cider.cook(sentences)):
+                counts = _cider.ngram_counts(sentence) if self.score_tables else None
                 for k in range(4):
                     for ngram, w in vec.weights[k].items():
                         ent_tok.append([tid(t) for t in ngram] + [-1] * (3 - k))
                         ent_w.append(w)
+                        if counts is not None:
+                            ent_tf.append(counts[ngram])
                     ent_start.append(self._n_ent + len(ent_w))
                 norms.append(vec.norm)
                 lens.append(vec.length)
+                if counts is not None:
+                    words.append(len(sentence.split()))
+                    seq_tok.extend(tid(t) for t in sentence.split(' '))  # ROUGE's split: '' is one empty token
+                    seq_start.append(self._n_seq + len(seq_tok))
             n_ref += len(sentences)
             ref_start.append(n_ref)
         self._n_ent += len(ent_w)
@@ -257,6 +282,12 @@ class DeviceCider(object):
             self.ref_ent_start.append(np.asarray(ent_start, np.int32))
             self.ref_norm.append(np.asarray(norms, np.float64))
             self.ref_len.append(np.asarray(lens, np.int32))
+            if self.score_tables:
+                self._n_seq += len(seq_tok)
+                self.ent_tf.append(np.asarray(ent_tf, np.int32))
+                self.ref_words.append(np.asarray(words, np.int32))
+                self.seq_start.append(np.asarray(seq_start, np.int32))
+                self.seq_tok.append(np.asarray(seq_tok, np.int32))
         self.slot_ref_start.append(np.asarray(ref_start, np.int32))
         self._tables = None
 
@@ -266,7 +297,8 @@ class DeviceCider(object):
 
     def host_arrays(self):
         """The packed arrays as numpy (tests walk them)."""
-        return {'expansion': self._exp_host, 'word_meta': self._meta_host, 'idf_key': self.idf_key.cpu().numpy(),
+        extra = {k: getattr(self, k).numpy() for k in ('ent_tf', 'ref_words', 'seq_start', 'seq_tok')} if self.score_tables else {}
+        return {**extra, 'expansion': self._exp_host, 'word_meta': self._meta_host, 'idf_key': self.idf_key.cpu().numpy(),
                 'idf_val': self.idf_val.cpu().numpy(), 'idf_start': list(self.idf_start),
                 'slot_ref_start': self.slot_ref_start.numpy(), 'ref_ent_start': self.ref_ent_start.numpy(),
                 'ent_tok': self.ent_tok.numpy(), 'ent_w': self.ent_w.numpy(), 'ref_norm': self.ref_norm.numpy(),

@@ -50,6 +50,8 @@
  *                           (models/caption/cap_generator.py:44-56): masks, concatenations, sigmoids, products, sum, scale
  *   grit_cider_reward    <- the self-critical reward, engine/caption_engine.py:433-438 (text_field.decode, PTBTokenizer.tokenize,
  *                           cider.compute_score) and datasets/caption/metrics/cider/cider_scorer.py (counts2vec, sim, compute_cider)
+ *   grit_caption_scores  <- the evaluation's scores, engine/caption_engine.py:165-190 (decode, itertools.groupby, PTBTokenizer.tokenize,
+ *                           compute_scores) and datasets/caption/metrics/{bleu/bleu_scorer.py, rouge/rouge.py, cider/cider_scorer.py}
  * (none of the last thirteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops)
  */
 #ifndef GRIT_HIP_H
@@ -61,7 +63,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 46
+#define GRIT_ABI_VERSION 47
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -813,6 +815,39 @@ typedef struct {
 } grit_cider_tables;
 int grit_cider_reward(const int64_t* tokens, int rows, int T, const int32_t* slots, int beam, const grit_cider_tables* tab,
                       float* out32, double* out64, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The evaluation's caption scores (reference engine/caption_engine.py:165-190: decode the best beam up to <eos>, collapse repeated
+ * words, PTB-tokenise, metrics.compute_scores): per hypothesis row the integers of BLEU-1..4 (bleu_scorer.py cook_test, option
+ * 'closest'), ROUGE-L (rouge.py, beta = 1.2) and CIDEr-D (as grit_cider_reward).  METEOR is not computed.  One launch, one workgroup
+ * per row, integer and float64 arithmetic in the host's order, no atomics: two launches on the same input are bit-identical.
+ *
+ * tokens [rows, T] int64, contiguous; slots [rows] int32 = the reference slot of each row; collapse != 0: every word id equal to
+ * its predecessor is dropped after the cut at the first <eos> (the evaluation does, the self-critical reward does not; with
+ * collapse == 0 the cider output equals grit_cider_reward's out64 bit for bit).
+ * comps [rows, GRIT_SCORE_COMPONENTS] int32 = testlen, the reference word count closest to it (a tie goes to the shorter),
+ * guess[4] = max(0, testlen - k), correct[4] = sum over the hypothesis' k-grams of min(count, max over references of its count);
+ * rouge [rows], cider [rows] float64.  An empty hypothesis is, for ROUGE-L, a sequence of one empty token (it scores 0 against a
+ * non-empty reference and 1 against an empty one).  A word id outside [0, vocab) in front of the first <eos>, or a slot outside
+ * [0, n_slots): -1 in every component and NaN in rouge and cider of that row.  Limits and `tab` as for grit_cider_reward; `ext` holds
+ * what BLEU and ROUGE need per reference, built by grit_amd/ops/caption_scores.py (DeviceCaptionScorer), device memory:
+ *   ent_tf [entries] int32          the raw count of the n-gram of tab->ent_tok[e] in its reference
+ *   ref_words [n_refs] int32        word count of the tokenised reference
+ *   seq_start [n_refs + 1], seq_tok the tokenised reference split at single spaces, CSR (an empty reference is the one token
+ *                                   empty_tok)
+ *   beta2                           the host's beta ** 2 as a double
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_SCORE_COMPONENTS 10
+typedef struct {
+    const int32_t* ent_tf;
+    const int32_t* ref_words;
+    const int32_t* seq_start;
+    const int32_t* seq_tok;
+    int empty_tok;
+    double beta2;
+} grit_score_tables;
+int grit_caption_scores(const int64_t* tokens, int rows, int T, const int32_t* slots, int collapse, const grit_cider_tables* tab,
+                        const grit_score_tables* ext, int32_t* comps, double* rouge, double* cider, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,10 @@ Phases follow the reference's epoch schedule (train_caption.py:92-147): fr_xe ->
 while the loader serves cached detector outputs, optimizers rebuilt when the mode flips between 'xe' and 'sc', and the best
 validation checkpoint loaded into the (wrapped) model before every self-critical epoch.  The self-critical phases need
 `dataloaders['train_dict']`, a `text_field` (decode) and the training captions for the CIDEr statistics; without them they are
-skipped (synthetic runs).
+skipped (synthetic runs).  With `dataloaders['valid_dict']` / `['test_dict']` and a `text_field` every epoch ends with the
+reference's evaluation (train_caption.py:149-179): beam search of the split, BLEU / ROUGE / CIDEr (`exp.eval_scorer`), and
+`checkpoint_best_{split}.pth` when `exp.save` is set and the CIDEr is the best so far -- the file the self-critical phase starts from.
+The best values travel in every epoch's checkpoint (`best_ciders`) and are restored by `exp.resume_from`.
 """
 import argparse
 import os
@@ -29,7 +32,7 @@ from grit_amd.amp import Bf16Compute
 from grit_amd.ddp import BucketedDataParallel
 from grit_amd.tuning import load_tuned_gemms
 from engine.caption_engine import *  # noqa: F401,F403  (reference does the same star import)
-from engine.caption_engine import build_optimizers, save_checkpoint, train_sc, train_xe
+from engine.caption_engine import build_optimizers, evaluate_metrics, save_checkpoint, train_sc, train_xe
 from models.caption import Transformer
 from models.caption.detector import build_detector
 from utils.cap_scheduler import CosineLRScheduler
@@ -93,6 +96,7 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
         model = BucketedDataParallel(model)
     optimizers = build_optimizers(model, config, mode='xe')
     resume = getattr(config.exp, 'resume_from', '')
+    resumed_best = None
     if resume:  # reference-format checkpoint (engine/caption_engine.py save_checkpoint): weights (+ optimizer state when present)
         ckpt = torch.load(resume, map_location='cpu')
         raw.load_state_dict(ckpt['state_dict'], strict=False)  # reaches the fp32 masters through the wrapper's hook
@@ -103,6 +107,7 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
                 except (ValueError, KeyError) as e:  # a checkpoint of another phase / parameter grouping
                     print(f"optimizer state of '{k}' not restored: {e}")
         start_epoch = max(start_epoch, int(ckpt.get('epoch', -1)) + 1)
+        resumed_best = ckpt.get('best_ciders')
 
     if dataloaders is None:
         steps = getattr(config.exp, 'synthetic_steps', 20)
@@ -114,6 +119,16 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
     total = xe_epochs + opt.freezing_sc_epochs + opt.finetune_sc_epochs
     can_sc = 'train_dict' in dataloaders and text_field is not None and cider is not None
     save = getattr(config.exp, 'save', False)
+    eval_scorer = getattr(config.exp, 'eval_scorer', 'device')
+    evaluates = text_field is not None and ('valid_dict' in dataloaders or 'test_dict' in dataloaders)
+    if evaluates and eval_scorer not in ('host', 'device'):
+        raise ValueError("exp.eval_scorer must be 'host' or 'device', not %r" % (eval_scorer,))
+    if evaluates and eval_scorer == 'device' and not use_cuda:  # said before the first epoch, not after it
+        raise ValueError("exp.eval_scorer='device' scores the captions in a HIP kernel and there is no GPU: set exp.eval_scorer='host'")
+    # carried across epochs and, through every epoch's checkpoint, across a resume (reference best_cider_val / best_cider_test)
+    best_cider = {'valid': 0.0, 'test': 0.0}
+    if resumed_best is not None and len(resumed_best) == 2:
+        best_cider = {'valid': float(resumed_best[0]), 'test': float(resumed_best[1])}
     results = []
     for epoch in range(start_epoch, min(total, getattr(config.exp, 'max_epochs', total))):
         phase = phase_of(epoch, opt)
@@ -139,10 +154,20 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
             res = train_sc(model, dataloaders, optimizers=optimizers, cider=cider, text_field=text_field,
                            tokenizer_pool=tokenizer_pool, device=device, epoch=epoch, config=config, rank=rank, writer=None,
                            evaluate='valid' in dataloaders, checkpoint=save)
+        # reference :149-179: rank 0 scores the validation split, rank 1 the test split (a single rank does both)
+        for split, owner in (('valid', 0), ('test', 1 if world > 1 else 0)):
+            if rank != owner or text_field is None or split + '_dict' not in dataloaders:
+                continue
+            scores = {}
+            evaluate_metrics(model, optimizers, dataloaders[split + '_dict'], text_field, epoch=epoch, split=split, config=config,
+                             train_res=res, best_cider=best_cider[split], which=phase, scheduler=scheduler, log_and_save=save,
+                             scorer=eval_scorer, scores_out=scores)
+            best_cider[split] = max(best_cider[split], scores['CIDEr'])
+            res[split + '_scores'], res['best_cider_' + split] = scores, best_cider[split]
         results.append(res)
         if rank == 0 and save:
-            save_checkpoint(model, optimizers, epoch=epoch, scores=[], best_ciders=[0, 0], config=config,
-                            filename=f'checkpoint_{phase}.pth', scheduler=scheduler)
+            save_checkpoint(model, optimizers, epoch=epoch, scores=[], best_ciders=[best_cider['valid'], best_cider['test']],
+                            config=config, filename=f'checkpoint_{phase}.pth', scheduler=scheduler)
         dist.barrier()
     if dist.is_initialized() and getattr(config.exp, 'destroy_group', True):
         dist.destroy_process_group()
