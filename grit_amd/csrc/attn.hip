@@ -13,7 +13,9 @@
 //             lane = key (q[d] arrives as an SGPR via v_readlane), softmax statistics by wave shuffles,
 //             output with lane = channel (p[j] broadcast by v_readlane).  Row log-sum-exp is kept for backward.
 //   backward: workgroup = one (batch, head), 8 waves.  P is recomputed from the saved log-sum-exp (no max/sum
-//             pass), delta = rowsum(dO*O) by a wave reduction, dQ with lane = channel, dK/dV accumulated in
+//             pass), delta = sum_k P dP by a wave reduction over the P and dP that form dS (not rowsum(dO*O): with bf16
+//             storage the saved output is rounded, and that rounding times dO is an absolute error of dS at the
+//             dominant key of a saturated row; `out` is kept in the ABI and not read), dQ with lane = channel, dK/dV accumulated in
 //             LDS with ds_add_f32 (all rows of a head meet in one workgroup, so no global atomics) and
 //             written once.
 //   dropout : keep-mask from a counter hash of (seed, flat index of P); forward and backward regenerate the
@@ -169,8 +171,6 @@ void attn_bwd_kernel(const T* __restrict__ q, long ldq, long bsq, const T* __res
         const size_t orow = ((size_t)b * Tq + r) * ((size_t)H * kD) + (size_t)h * kD + lane;
         const float qd = ld(q + (size_t)b * bsq + (size_t)r * ldq + (size_t)h * kD + lane);
         const float god = ld(dout + orow);
-        const float od = ld(out + orow);
-        const float delta = wave_sum(god * od);
         const float row_lse = lse[(size_t)bh * Tq + r];
 
         // lane = key: s = q.K[j], dpd = dO.V[j]; each lane walks its own 256-byte K / V row
@@ -193,15 +193,27 @@ void attn_bwd_kernel(const T* __restrict__ q, long ldq, long bsq, const T* __res
         }
         const uint8_t* mrow = mask ? mask + (size_t)b * msb + (size_t)r * msq : nullptr;
         const unsigned long long pbase = ((unsigned long long)bh * Tq + r) * (unsigned long long)Nk;
+        float mk[kChunks], part = 0.f;  // s[c] becomes P, mk[c] the dropout factor
+#pragma unroll
+        for (int c = 0; c < kChunks; ++c) {
+            const int j = lane + 64 * c;
+            float p = 0.f;
+            mk[c] = 1.0f;
+            if (j < Nk) {
+                p = expf(s[c] * scale - row_lse);
+                if (mrow && mrow[j]) p = 0.f;
+                if (drop_p > 0.f) mk[c] = keep_scale(seed, pbase + j, drop_p, inv_keep);
+                part = fmaf(p * mk[c], dp[c], part);
+            }
+            s[c] = p;
+        }
+        const float delta = wave_sum(part);  // sum_k P keep dP
 #pragma unroll
         for (int c = 0; c < kChunks; ++c) {
             const int j = lane + 64 * c;
             if (j < Nk) {
-                float p = expf(s[c] * scale - row_lse);
-                if (mrow && mrow[j]) p = 0.f;
-                const float m = drop_p > 0.f ? keep_scale(seed, pbase + j, drop_p, inv_keep) : 1.0f;
-                ds_w[j] = p * (m * dp[c] - delta) * scale;
-                pd_w[j] = p * m;
+                ds_w[j] = s[c] * (mk[c] * dp[c] - delta) * scale;
+                pd_w[j] = s[c] * mk[c];
             }
         }
         // (same wave wrote and reads: LDS ops of one wave are issued in order, a wave barrier is enough)

@@ -8,6 +8,9 @@
 // directly the B operand of O^T = V^T P^T (V^T fragments via ds_read_b64_tr_b16 from the row-major V tile).
 // Backward: phase 1 wave w = key tile w (P from the saved log2-sum-exp2, dP, dS, dV^T, dK^T), dS crosses LDS once
 // (transposed), phase 2 wave w = query tile w (dQ^T).  One workgroup owns all rows of its (batch, head): no atomics.
+// delta = sum_k P dP is summed in fp32 from the same P and dP that form dS (each key-tile wave leaves its partial row sums in
+// LDS, added in tile order: deterministic).  The identity delta = rowsum(dO * O) would read the STORED bf16 output, whose rounding
+// (2^-9 relative) times dO is an absolute error of dS at the dominant key of a saturated row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/grit_hip.h"
@@ -156,7 +159,7 @@ void attn_mfma_fwd(const __bf16* __restrict__ q, long ldq, long bsq, const __bf1
 __global__ __launch_bounds__(640)
 void attn_mfma_bwd(const __bf16* __restrict__ q, long ldq, long bsq, const __bf16* __restrict__ k, long ldk, long bsk,
                    const __bf16* __restrict__ v, long ldv, long bsv, const uint8_t* __restrict__ mask, long msb, long msq,
-                   const __bf16* __restrict__ out, const __bf16* __restrict__ dout, const float* __restrict__ lse2,
+                   const __bf16* __restrict__ dout, const float* __restrict__ lse2,
                    int H, int Tq, int Nk, float scale, float drop_p, unsigned long long seed,
                    const unsigned long long* __restrict__ seed_dev, __bf16* __restrict__ dq, __bf16* __restrict__ dk,
                    __bf16* __restrict__ dv) {
@@ -167,6 +170,7 @@ void attn_mfma_bwd(const __bf16* __restrict__ q, long ldq, long bsq, const __bf1
     __shared__ __attribute__((aligned(16))) __bf16 dSt[kRows * kSP];  // [key][query]
     __shared__ __attribute__((aligned(16))) float lse_s[kRows];
     __shared__ __attribute__((aligned(16))) float delta_s[kRows];
+    __shared__ __attribute__((aligned(16))) float part_s[kT * kRows];  // [key tile][query]: partial sum_k P dP
     const int bh = blockIdx.x, b = bh / H, h = bh % H;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, lg = lane >> 4;
     const int trq = l15 >> 2, trp = l15 & 3;
@@ -175,23 +179,12 @@ void attn_mfma_bwd(const __bf16* __restrict__ q, long ldq, long bsq, const __bf1
 
     stage_tile(Qs, q + (size_t)b * bsq + (size_t)h * kD, ldq, Tq);
     stage_tile(Ks, k + (size_t)b * bsk + (size_t)h * kD, ldk, Nk);
-    // dO tile + delta = rowsum(dO * O): 8 threads per row, 8 channels each
+    // dO tile: 8 threads per row, 8 channels each
     for (int i = tid; i < kRows * 8; i += blockDim.x) {
         const int row = i >> 3, c = i & 7;
         uint4 g4 = make_uint4(0, 0, 0, 0);
-        float part = 0.f;
-        if (row < Tq) {
-            const size_t off = ((size_t)b * Tq + row) * orow_stride + (size_t)h * kD + c * 8;
-            g4 = *reinterpret_cast<const uint4*>(dout + off);
-            const v8bf a = __builtin_bit_cast(v8bf, g4), o8 = ld8(out + off);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) part = fmaf((float)a[e], (float)o8[e], part);
-        }
-        part += __shfl_xor(part, 1, 64);
-        part += __shfl_xor(part, 2, 64);
-        part += __shfl_xor(part, 4, 64);
+        if (row < Tq) g4 = *reinterpret_cast<const uint4*>(dout + ((size_t)b * Tq + row) * orow_stride + (size_t)h * kD + c * 8);
         *reinterpret_cast<uint4*>(&dOs[row * kP + c * 8]) = g4;
-        if (c == 0) delta_s[row] = part;
     }
     for (int i = tid; i < kRows; i += blockDim.x) lse_s[i] = i < Tq ? lse2[(size_t)bh * Tq + i] * kLog2e : 0.f;
     for (int i = tid; i < (kRows - 16 * nkt) * kSP; i += blockDim.x) dSt[16 * nkt * kSP + i] = (__bf16)0.f;
@@ -202,36 +195,80 @@ void attn_mfma_bwd(const __bf16* __restrict__ q, long ldq, long bsq, const __bf1
     const v4bf z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
 
     // ================= phase 1: wave w = key tile w =================
+    const int key = 16 * w + l15, keyc = min(key, Nk - 1);
+    const __bf16* krow = k + (size_t)b * bsk + (size_t)keyc * ldk + (size_t)h * kD + lg * 8;
+    const __bf16* vrow = v + (size_t)b * bsv + (size_t)keyc * ldv + (size_t)h * kD + lg * 8;
+    v8bf kf0 = {}, kf1 = {}, vf0 = {}, vf1 = {};
+    if (w < nkt) { kf0 = ld8(krow); kf1 = ld8(krow + 32); vf0 = ld8(vrow); vf1 = ld8(vrow + 32); }  // query-only waves load nothing
+    // S, dP, exp2 and the dropout hash are evaluated twice, once per pass below: deliberate -- four MFMAs and four exp2 per tile cost
+    // less than holding p and dP of ten query tiles (80 registers) across the barrier between the passes.
+    // P (before dropout), the dropout factor and dP of this lane's key against queries 16 qt + 4 lg + {0..3}
+    auto tile = [&](int qt, float* p, float* mk, v4f& dp) {
+        const __bf16* qr = &Qs[(16 * qt + l15) * kP + lg * 8];
+        const __bf16* dr = &dOs[(16 * qt + l15) * kP + lg * 8];
+        v4f s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(qr), kf0, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(qr + 32), kf1, s, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(dr), vf0, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(dr + 32), vf1, dp, 0, 0, 0);
+        const float4 lq = *reinterpret_cast<const float4*>(&lse_s[16 * qt + 4 * lg]);
+        const float lqa[4] = {lq.x, lq.y, lq.z, lq.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int qi = 16 * qt + 4 * lg + r;
+            const bool dead = key >= Nk || qi >= Tq || (mask && mask[(size_t)b * msb + (size_t)min(qi, Tq - 1) * msq + keyc]);
+            p[r] = dead ? 0.f : __builtin_amdgcn_exp2f(s[r] * c2 - lqa[r]);
+            mk[r] = drop_p > 0.f
+                ? keep_scale(seed, ((unsigned long long)bh * Tq + min(qi, Tq - 1)) * (unsigned long long)Nk + keyc, drop_p, inv_keep)
+                : 1.0f;
+        }
+    };
+    // pass A: this key tile's share of delta[q] = sum_k P keep dP
     if (w < nkt) {
-        const int key = 16 * w + l15, keyc = min(key, Nk - 1);
-        const __bf16* krow = k + (size_t)b * bsk + (size_t)keyc * ldk + (size_t)h * kD + lg * 8;
-        const __bf16* vrow = v + (size_t)b * bsv + (size_t)keyc * ldv + (size_t)h * kD + lg * 8;
-        const v8bf kf0 = ld8(krow), kf1 = ld8(krow + 32), vf0 = ld8(vrow), vf1 = ld8(vrow + 32);
+#pragma unroll
+        for (int qt = 0; qt < kT; ++qt) {
+            if (qt < nqt) {
+                float p[4], mk[4];
+                v4f dp;
+                tile(qt, p, mk, dp);
+                float4 part;
+                float* pa = &part.x;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float t = p[r] * mk[r] * dp[r];
+                    t += __shfl_xor(t, 1, 64);
+                    t += __shfl_xor(t, 2, 64);
+                    t += __shfl_xor(t, 4, 64);
+                    t += __shfl_xor(t, 8, 64);
+                    pa[r] = t;
+                }
+                if (l15 == 0) *reinterpret_cast<float4*>(&part_s[w * kRows + 16 * qt + 4 * lg]) = part;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 16 * nqt; i += blockDim.x) {
+        float d = 0.f;
+        for (int t = 0; t < nkt; ++t) d += part_s[t * kRows + i];
+        delta_s[i] = d;
+    }
+    __syncthreads();
+    // pass B: dS, dV^T, dK^T
+    if (w < nkt) {
         v4bf Pp[kT];
 #pragma unroll
         for (int qt = 0; qt < kT; ++qt) {
             Pp[qt] = z4;
             v4bf sp = z4;
             if (qt < nqt) {
-                const __bf16* qr = &Qs[(16 * qt + l15) * kP + lg * 8];
-                const __bf16* dr = &dOs[(16 * qt + l15) * kP + lg * 8];
-                v4f s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(qr), kf0, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(qr + 32), kf1, s, 0, 0, 0);
-                v4f dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(dr), vf0, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ld8(dr + 32), vf1, dp, 0, 0, 0);
-                const float4 lq = *reinterpret_cast<const float4*>(&lse_s[16 * qt + 4 * lg]);
+                float p[4], mk[4];
+                v4f dp;
+                tile(qt, p, mk, dp);
                 const float4 dl = *reinterpret_cast<const float4*>(&delta_s[16 * qt + 4 * lg]);
-                const float lqa[4] = {lq.x, lq.y, lq.z, lq.w}, dla[4] = {dl.x, dl.y, dl.z, dl.w};
+                const float dla[4] = {dl.x, dl.y, dl.z, dl.w};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int qi = 16 * qt + 4 * lg + r;
-                    const bool dead = key >= Nk || qi >= Tq || (mask && mask[(size_t)b * msb + (size_t)min(qi, Tq - 1) * msq + keyc]);
-                    const float p = dead ? 0.f : __builtin_amdgcn_exp2f(s[r] * c2 - lqa[r]);
-                    const float mk = drop_p > 0.f
-                        ? keep_scale(seed, ((unsigned long long)bh * Tq + min(qi, Tq - 1)) * (unsigned long long)Nk + keyc, drop_p, inv_keep)
-                        : 1.0f;
-                    Pp[qt][r] = (__bf16)(p * mk);
-                    sp[r] = (__bf16)(p * (mk * dp[r] - dla[r]));
+                    Pp[qt][r] = (__bf16)(p[r] * mk[r]);
+                    sp[r] = (__bf16)(p[r] * (mk[r] * dp[r] - dla[r]));
                 }
             }
             *reinterpret_cast<v4bf*>(&dSt[(16 * w + l15) * kSP + 16 * qt + 4 * lg]) = sp;
@@ -327,11 +364,12 @@ int grit_attn_mfma_bwd(const void* q, long ldq, long bsq, const void* k, long ld
                        unsigned long long seed, const unsigned long long* seed_dev, void* dq, void* dk, void* dv,
                        hipStream_t st) {
     if (!fits(q, ldq, bsq, k, ldk, bsk, v, ldv, bsv, Tq, Nk, D)) return GRIT_ERR_UNSUPPORTED;
-    if ((uintptr_t)out % 16 || (uintptr_t)dout % 16 || (uintptr_t)dq % 16 || (uintptr_t)dk % 16 || (uintptr_t)dv % 16)
+    // (`out` stays in the interface of both families; neither backward reads it: delta comes from P and dP)
+    if ((uintptr_t)dout % 16 || (uintptr_t)dq % 16 || (uintptr_t)dk % 16 || (uintptr_t)dv % 16)
         return GRIT_ERR_UNSUPPORTED;
     const int waves = (max(Tq, Nk) + 15) / 16;
     hipLaunchKernelGGL(attn_mfma_bwd, dim3(B * H), dim3(64 * waves), 0, st, (const __bf16*)q, ldq, bsq, (const __bf16*)k,
-                       ldk, bsk, (const __bf16*)v, ldv, bsv, mask, msb, msq, (const __bf16*)out, (const __bf16*)dout, lse,
+                       ldk, bsk, (const __bf16*)v, ldv, bsv, mask, msb, msq, (const __bf16*)dout, lse,
                        H, Tq, Nk, scale, drop_p, seed, seed_dev, (__bf16*)dq, (__bf16*)dk, (__bf16*)dv);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }
