@@ -11,7 +11,13 @@
 // whole number of lanes (C/G % 8 == 0).  A workgroup (4 waves) walks a chunk of rows of one image.
 //   forward : gn_stats (per-chunk partial sum / sum of squares per group)  ->  gn_apply (folds the chunk partials,
 //             writes mean / rstd once, normalises)
-//   backward: gn_bwd_stats (per-chunk, per-channel sums of dy and dy*x)  ->  gn_bwd_apply (dx)  +  gn_bwd_params (dgamma, dbeta)
+//   backward: gn_bwd_stats (per-chunk, per-channel sums of dy and dy*(x - mean))  ->  gn_bwd_apply (dx)  +  gn_bwd_params (dgamma, dbeta)
+//
+// Numerics: the forward sums are taken of x - pivot, pivot = the group's first element x[b, 0, g*C/G] (every chunk of an
+// (image, group) reads the same one), so var = q/n - m*m is formed from a shifted mean m of the order of the spread, not
+// from the raw mean: with the raw one-pass sums a group with mean 30 / std 1 lost 10 bits of rstd (relative error 1e-4),
+// shifted it keeps fp32 accuracy.  For the same reason the normalisation is (x - mean) * (rstd*gamma) + beta, the backward
+// sums dy * (x - mean) rather than dy * x, and dx is built from x - mean: no term is a difference of two large products.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
@@ -68,7 +74,14 @@ __device__ __forceinline__ float fold_rows(float v) {
     return v;
 }
 
-// ---- forward statistics: partial[b][chunk][g] = (sum, sum of squares) over this chunk's rows and the group's channels
+// the value every partial sum of an (image, group) is shifted by: row 0 of the image, channel c0 = first of the group
+template <typename T>
+__device__ __forceinline__ float pivot(const T* xb, int c0) {
+    if constexpr (sizeof(T) == 4) return xb[c0];
+    else return __bfloat162float(xb[c0]);
+}
+
+// ---- forward statistics: partial[b][chunk][g] = (sum, sum of squares) of x - pivot over this chunk's rows and the group's channels
 template <typename T, int LPR>
 __global__ __launch_bounds__(256)
 void gn_stats(const T* __restrict__ x, long x_bstride, int Tn, int G, float* __restrict__ partial) {
@@ -78,15 +91,16 @@ void gn_stats(const T* __restrict__ x, long x_bstride, int Tn, int G, float* __r
     const int b = blockIdx.y;
     const Rows rr = chunk_rows(Tn);
     const T* xb = x + (size_t)b * x_bstride;
+    const int lpg = (C / G) / 8;  // lanes per group (power of two)
+    const float piv = pivot(xb, (sub / lpg) * lpg * 8);
     float s = 0.f, q = 0.f;
     for (int row = rr.r0 + wave * R + lane / LPR; row < rr.r1; row += 4 * R) {
         float v[8];
         V8<T>::load(xb + (size_t)row * C + sub * 8, v);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { s += v[i]; q = fmaf(v[i], v[i], q); }
+        for (int i = 0; i < 8; ++i) { const float d = v[i] - piv; s += d; q = fmaf(d, d, q); }
     }
     s = fold_rows<LPR>(s); q = fold_rows<LPR>(q);
-    const int lpg = (C / G) / 8;  // lanes per group (power of two)
     for (int o = 1; o < lpg; o <<= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
     if (lane < LPR) { red[wave][0][lane] = s; red[wave][1][lane] = q; }
     __syncthreads();
@@ -114,9 +128,10 @@ void gn_apply(const T* __restrict__ x, long x_bstride, const WT* __restrict__ w,
             q += partial[(((size_t)b * kChunks + c) * 2 + 1) * G + threadIdx.x];
         }
         const float n = (float)Tn * (float)(C / G);
-        const float mu = s / n;
-        const float var = fmaxf(q / n - mu * mu, 0.f);
+        const float m = s / n;  // mean of x - pivot
+        const float var = fmaxf(q / n - m * m, 0.f);
         const float rs = rsqrtf(var + eps);
+        const float mu = pivot(x + (size_t)b * x_bstride, (int)threadIdx.x * (C / G)) + m;
         mu_s[threadIdx.x] = mu; rs_s[threadIdx.x] = rs;
         if (blockIdx.x == 0) { mean[b * G + threadIdx.x] = mu; rstd[b * G + threadIdx.x] = rs; }
     }
@@ -127,7 +142,7 @@ void gn_apply(const T* __restrict__ x, long x_bstride, const WT* __restrict__ w,
     V8<WT>::load(w + sub * 8, wv);
     V8<WT>::load(bias + sub * 8, bv);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { wv[i] *= rs; bv[i] = fmaf(-mu, wv[i], bv[i]); }  // y = x * (rs*gamma) + (beta - mu*rs*gamma)
+    for (int i = 0; i < 8; ++i) wv[i] *= rs;  // y = (x - mu) * (rs*gamma) + beta
     const Rows rr = chunk_rows(Tn);
     const T* xb = x + (size_t)b * x_bstride;
     T* yb = y + (size_t)b * y_bstride;
@@ -135,16 +150,16 @@ void gn_apply(const T* __restrict__ x, long x_bstride, const WT* __restrict__ w,
         float v[8];
         V8<T>::load(xb + (size_t)row * C + sub * 8, v);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaf(v[i], wv[i], bv[i]);
+        for (int i = 0; i < 8; ++i) v[i] = fmaf(v[i] - mu, wv[i], bv[i]);
         V8<T>::store(yb + (size_t)row * C + sub * 8, v);
     }
 }
 
-// ---- backward statistics: partial[b][chunk][0][c] = sum_rows dy*x, [1][c] = sum_rows dy
+// ---- backward statistics: partial[b][chunk][0][c] = sum_rows dy*(x - mean), [1][c] = sum_rows dy
 template <typename T, int LPR>
 __global__ __launch_bounds__(256)
-void gn_bwd_stats(const T* __restrict__ x, long x_bstride, const T* __restrict__ dy, long dy_bstride, int Tn,
-                  float* __restrict__ partial) {
+void gn_bwd_stats(const T* __restrict__ x, long x_bstride, const T* __restrict__ dy, long dy_bstride,
+                  const float* __restrict__ mean, int Tn, int G, float* __restrict__ partial) {
     constexpr int C = LPR * 8, R = 64 / LPR;
     __shared__ float red[4][2][C];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane % LPR;
@@ -152,13 +167,14 @@ void gn_bwd_stats(const T* __restrict__ x, long x_bstride, const T* __restrict__
     const Rows rr = chunk_rows(Tn);
     const T* xb = x + (size_t)b * x_bstride;
     const T* gb = dy + (size_t)b * dy_bstride;
+    const float mu = mean[b * G + (sub * 8) / (C / G)];
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int row = rr.r0 + wave * R + lane / LPR; row < rr.r1; row += 4 * R) {
         float v[8], g[8];
         V8<T>::load(xb + (size_t)row * C + sub * 8, v);
         V8<T>::load(gb + (size_t)row * C + sub * 8, g);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { a[i] = fmaf(g[i], v[i], a[i]); s[i] += g[i]; }
+        for (int i = 0; i < 8; ++i) { a[i] = fmaf(g[i], v[i] - mu, a[i]); s[i] += g[i]; }
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -173,7 +189,8 @@ void gn_bwd_stats(const T* __restrict__ x, long x_bstride, const T* __restrict__
     }
 }
 
-// ---- backward apply: dx = rs*gamma*dy - rs*(db_g + xhat*ds_g)/n   with ds_g = sum_c gamma_c*rs*(A_c - mu*B_c), db_g = sum_c gamma_c*B_c
+// ---- backward apply: dx = rs*gamma*dy - rs*(db_g + xhat*ds_g)/n   with ds_g = sum_c gamma_c*rs*A_c, db_g = sum_c gamma_c*B_c
+// (A_c = sum dy*(x - mu), B_c = sum dy over the image's rows)
 template <typename T, typename WT, int LPR>
 __global__ __launch_bounds__(256)
 void gn_bwd_apply(const T* __restrict__ x, long x_bstride, const T* __restrict__ dy, long dy_bstride,
@@ -197,14 +214,14 @@ void gn_bwd_apply(const T* __restrict__ x, long x_bstride, const T* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float A = AB[0][sub * 8 + i], Bv = AB[1][sub * 8 + i];
-        ds = fmaf(wv[i], A - mu * Bv, ds);
+        ds = fmaf(wv[i], A, ds);
         db = fmaf(wv[i], Bv, db);
     }
     for (int o = 1; o < lpg; o <<= 1) { ds += __shfl_xor(ds, o, 64); db += __shfl_xor(db, o, 64); }
     ds *= rs;  // sum over the group of gamma*dy*xhat
     const float inv_n = 1.0f / ((float)Tn * (float)cpg);
-    // dx = c1*dy + c2*x + c3 with c1 = rs*gamma, c2 = -rs*rs*ds/n, c3 = -c2*mu - rs*db/n
-    const float c2 = -rs * rs * ds * inv_n, c3 = -c2 * mu - rs * db * inv_n;
+    // dx = c1*dy + c2*(x - mu) + c3 with c1 = rs*gamma, c2 = -rs*rs*ds/n, c3 = -rs*db/n
+    const float c2 = -rs * rs * ds * inv_n, c3 = -rs * db * inv_n;
 #pragma unroll
     for (int i = 0; i < 8; ++i) wv[i] *= rs;
     const Rows rr = chunk_rows(Tn);
@@ -216,15 +233,15 @@ void gn_bwd_apply(const T* __restrict__ x, long x_bstride, const T* __restrict__
         V8<T>::load(xb + (size_t)row * C + sub * 8, v);
         V8<T>::load(gb + (size_t)row * C + sub * 8, gg);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = fmaf(gg[i], wv[i], fmaf(v[i], c2, c3));
+        for (int i = 0; i < 8; ++i) v[i] = fmaf(gg[i], wv[i], fmaf(v[i] - mu, c2, c3));
         V8<T>::store(ob + (size_t)row * C + sub * 8, v);
     }
 }
 
-// ---- parameter gradients: dgamma_c = sum_b rs_bg*(A_bc - mu_bg*B_bc), dbeta_c = sum_b B_bc
+// ---- parameter gradients: dgamma_c = sum_b rs_bg*A_bc, dbeta_c = sum_b B_bc
 template <typename WT>
 __global__ __launch_bounds__(256)
-void gn_bwd_params(const float* __restrict__ partial, const float* __restrict__ mean, const float* __restrict__ rstd, int B,
+void gn_bwd_params(const float* __restrict__ partial, const float* __restrict__ rstd, int B,
                    int C, int G, WT* __restrict__ dgamma, WT* __restrict__ dbeta) {
     // 64 channels per workgroup, the images spread over the 4 waves (a single thread walking B x chunks partials is a
     // 1 000-deep dependent-latency chain)
@@ -241,7 +258,7 @@ void gn_bwd_params(const float* __restrict__ partial, const float* __restrict__ 
                 A += partial[(((size_t)b * kChunks + k) * 2 + 0) * C + c];
                 Bv += partial[(((size_t)b * kChunks + k) * 2 + 1) * C + c];
             }
-            dg = fmaf(rstd[b * G + g], A - mean[b * G + g] * Bv, dg);
+            dg = fmaf(rstd[b * G + g], A, dg);
             dbv += Bv;
         }
     }
@@ -299,10 +316,10 @@ int grit_groupnorm_tokens_bwd(const void* x, long x_bstride, const void* dy, lon
 #define GRIT_GN_BWD(T_, WT_, LPR_)                                                                                          \
     {                                                                                                                       \
         hipLaunchKernelGGL((gn_bwd_stats<T_, LPR_>), grid, block, 0, st, (const T_*)x, x_bstride, (const T_*)dy, dy_bstride, \
-                           T, workspace);                                                                                   \
+                           mean, T, G, workspace);                                                                          \
         hipLaunchKernelGGL((gn_bwd_apply<T_, WT_, LPR_>), grid, block, 0, st, (const T_*)x, x_bstride, (const T_*)dy,       \
                            dy_bstride, (const WT_*)weight, mean, rstd, T, G, workspace, (T_*)dx);                           \
-        hipLaunchKernelGGL((gn_bwd_params<WT_>), dim3((C + 63) / 64), block, 0, st, workspace, mean, rstd, B, C, G,      \
+        hipLaunchKernelGGL((gn_bwd_params<WT_>), dim3((C + 63) / 64), block, 0, st, workspace, rstd, B, C, G,            \
                            (WT_*)dweight, (WT_*)dbias);                                                                     \
     }
     if (x_is_bf16 && w_is_bf16) { if (C == 512) GRIT_GN_BWD(__hip_bfloat16, __hip_bfloat16, 64) else GRIT_GN_BWD(__hip_bfloat16, __hip_bfloat16, 32) }
