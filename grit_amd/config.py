@@ -70,6 +70,37 @@ def default_config(**overrides):
     return to_config(raw)
 
 
+_DETECTION_DEFAULTS = {
+    'exp': dict(seed=42, save_dir='', rank=0, ngpus_per_node=8, world_size=64, checkpoint='', eval=False, resume=False,
+                eval_every_iters=-1),
+    'model': dict(
+        has_attr_head=False,
+        backbone=dict(backbone_name='swin_base_win7_384_22k', pre_trained='imagenet'),
+        det_module=dict(reduced_dim=512, dim_feedforward=1024, num_heads=8, num_layers=6, num_levels=4, num_points=4,
+                        return_intermediate=True, num_queries=150, num_classes=1849, dropout=0.1, activation='relu',
+                        with_box_refine=True, aux_loss=True,
+                        loss=dict(dice_loss_coef=1., cls_loss_coef=2., bbox_loss_coef=5., giou_loss_coef=2., attr_loss_coef=0.,
+                                  eos_coef=0.1, focal_alpha=0.25),
+                        matcher=dict(set_cost_class=2.0, set_cost_bbox=5.0, set_cost_giou=2.0))),
+    'optimizer': dict(lr=1e-5, lr_backbone=2e-5, batch_size=4, weight_decay=1e-4, lr_drop_epochs=[40], scheduler='step',
+                      decay_rate=0.1, clip_max_norm=0.1, num_workers=4, num_epochs=50),
+}
+
+
+def detection_config(**overrides):
+    """The detector pre-training configuration (the keys of configs/detection/train_config.yaml) as a namespace; dotted overrides
+    as in default_config.  The dataset groups of the yaml are not part of it: the Visual Genome readers are out of scope."""
+    import copy
+    raw = copy.deepcopy(_DETECTION_DEFAULTS)
+    for dotted, value in overrides.items():
+        node = raw
+        *path, leaf = dotted.split('.')
+        for p in path:
+            node = node.setdefault(p, {})
+        node[leaf] = value
+    return to_config(raw)
+
+
 def load_yaml(path):
     import yaml
     with open(path) as f:

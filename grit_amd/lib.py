@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgrit_hip.so")
-ABI_VERSION = 47
+ABI_VERSION = 49
 
 _c = ctypes
 _ptr, _int, _i64, _f32, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -98,7 +98,15 @@ SIGNATURES = {
     "grit_gemm_bf16_nt_rows": [_ptr, _c.c_long] * 3 + [_int] * 4 + [_ptr, _ptr, _c.c_long, _ptr, _ptr, _int, _int, _ptr],
     "grit_cider_reward": [_ptr, _int, _int, _ptr, _int, _ptr, _ptr, _ptr, _ptr],
     "grit_caption_scores": [_ptr, _int, _int, _ptr, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "grit_det_match_f32": [_ptr] * 5 + [_int] * 5 + [_f32] * 3 + [_ptr, _int, _ptr, _ptr, _ptr],
+    "grit_lsa_f32": [_ptr, _ptr, _ptr, _int, _int, _int, _int, _ptr, _ptr, _ptr],
+    "grit_det_loss_fwd_f32": [_ptr] * 6 + [_int] * 4 + [_f32] + [_ptr] * 5,
+    "grit_det_loss_bwd_f32": [_ptr] * 6 + [_int] * 4 + [_f32, _ptr, _ptr, _int, _ptr, _ptr, _ptr],
 }
+
+DET_MAX_SIDE = 512  # GRIT_DET_MAX_SIDE
+DET_LOSS_ROWS = 20  # GRIT_DET_LOSS_ROWS
+DET_LOSS_FIELDS = 8  # GRIT_DET_LOSS_FIELDS
 
 SLAB_GROUP_MAX = 48  # GRIT_SLAB_GROUP_MAX
 WGRAD_GROUP_MAX = 32  # GRIT_WGRAD_GROUP_MAX

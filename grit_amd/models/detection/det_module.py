@@ -9,7 +9,8 @@ depends on: level_embed is never added, box refinement feeds `.detac
 
 MI355X specifics: the 150x150 self-attention runs through the fused attention kernel (the
 nn.MultiheadAttention object only owns the parameters, so in_proj_weight/in_proj_bias/out_proj keys are
-unchanged), and the cross-attention samples the value maps with the HIP MSDeformAttn op.
+unchanged), and the cross-attention samples the value maps with the HIP MSDeformAttn op.  `detection_head` (:219-271)
+turns the stacks into the class logits and boxes detector pre-training supervises.
 """
 import copy
 import math
@@ -330,6 +331,42 @@ class DetectionModule(nn.Module):
         if self.return_intermediate:
             return torch.stack(hs), init_reference_out, torch.stack(refs)
         return od['tgt'], init_reference_out, od['reference_points']
+
+
+    def _head(self, lvl, hidden, reference):
+        """Class logits and the box of one output level: the box MLP predicts an offset in logit space from `reference` (2-d
+        references move the centre only).  Box arithmetic in fp32."""
+        class_embed = self.class_embed[lvl] if isinstance(self.class_embed, nn.ModuleList) else self.class_embed
+        bbox_embed = self.bbox_embed[lvl] if isinstance(self.bbox_embed, nn.ModuleList) else self.bbox_embed
+        logits = class_embed(hidden)
+        delta = bbox_embed(hidden).float()
+        anchor = inverse_sigmoid(reference.float())
+        if anchor.shape[-1] == 4:
+            delta = delta + anchor
+        else:
+            assert anchor.shape[-1] == 2
+            delta = torch.cat([delta[..., :2] + anchor, delta[..., 2:]], -1)
+        return logits, delta.sigmoid()
+
+    def detection_head(self, hs, init_reference, inter_references):
+        """hs [levels, B, Q, C], init_reference [B, Q, 2 | 4], inter_references [levels, B, Q, 2 | 4] (what forward returns with
+        last_only=False) -> {'pred_logits' [B, Q, K], 'pred_boxes' [B, Q, 4]} and, in training with aux_loss, 'aux_outputs': the same
+        pair for every level but the last.  As the reference (det_module.py:219-271): in training level 0 starts from init_reference
+        and level l > 0 from inter_references[l - 1] -- inter_references[0] IS the initial reference, so levels 0 and 1 share it; in
+        evaluation only the last head runs, from inter_references[-2].  In training the stacks themselves ride along as
+        'pred_logits_all' [levels, B, Q, K] and 'pred_boxes_all' [levels, B, Q, 4] (only when aux_loss hands out every level), so that
+        the criterion reads all levels without stacking them again."""
+        if not self.training:
+            logits, boxes = self._head(-1, hs[-1], inter_references[-2])
+            return {'pred_logits': logits, 'pred_boxes': boxes}
+        levels = [self._head(lvl, hs[lvl], init_reference if lvl == 0 else inter_references[lvl - 1]) for lvl in range(hs.shape[0])]
+        logits = torch.stack([l for l, _ in levels])
+        boxes = torch.stack([b for _, b in levels])
+        out = {'pred_logits': logits[-1], 'pred_boxes': boxes[-1]}
+        if self.aux_loss and self.num_decoder_layers > 0:
+            out['aux_outputs'] = [{'pred_logits': l, 'pred_boxes': b} for l, b in zip(logits[:-1], boxes[:-1])]
+            out['pred_logits_all'], out['pred_boxes_all'] = logits, boxes
+        return out
 
 
 def build_det_module_with_config(cfg):

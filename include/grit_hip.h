@@ -63,7 +63,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 47
+#define GRIT_ABI_VERSION 49
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -848,6 +848,63 @@ typedef struct {
 } grit_score_tables;
 int grit_caption_scores(const int64_t* tokens, int rows, int T, const int32_t* slots, int collapse, const grit_cider_tables* tab,
                         const grit_score_tables* ext, int32_t* comps, double* rouge, double* cider, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Detector set criterion (reference models/detection/od_losses.py: HungarianMatcher :359-431, SetCriterion :68-323): the matching
+ * of predictions to targets and the losses of ALL output layers of a step, on the device, with no host round trip.  fp32 tensors
+ * (the caller casts the heads' outputs with .float(); there is no bf16 form); duals, path lengths and sums in float64.
+ *
+ * A "problem" is one (output layer, image) pair, p = layer * B + image, P = L * B.  Targets arrive packed over the batch:
+ * tgt_labels [sum T] int64, tgt_boxes [sum T, 4] (cxcywh, normalised), tgt_offsets [B + 1] int32 (device memory, like the rest).
+ *
+ * grit_det_match_f32: one launch, one wave per problem.  It writes the cost
+ *     C[q, t] = w_bbox * |box_q - box_t|_1 + w_class * (pos - neg)(sigmoid(logit[q, label_t])) - w_giou * GIoU(box_q, box_t),
+ *     pos = 0.25 (1 - p)^2 (-log(p + 1e-8)),  neg = 0.75 p^2 (-log(1 - p + 1e-8))        (od_losses.py:413-426, box_ops.py:32-69)
+ * in fp32, uncontracted, to cost [P, Q, ld] (ld >= Tmax; the caller's workspace, and what a test reads), then solves each problem
+ * by shortest augmenting paths over its smaller side (Jonker-Volgenant / Crouse 2016, the algorithm of
+ * scipy.optimize.linear_sum_assignment) with float64 duals: the exact optimum of the fp32 matrix as stored, for any T >= 0.  With
+ * T > Q, Q pairs are matched and T - Q targets stay unmatched.
+ *     match_q [P, Tmax] int32: the query of each target, -1 for an unmatched target and for t >= T
+ *     match_t [P, Q]    int32: the target (index within its image) of each query, or -1
+ * A label outside [0, K) or a non-finite cost that leaves a row without a finite path leaves the whole problem unmatched (-1).
+ * BOUND: Q <= GRIT_DET_MAX_SIDE and Tmax <= GRIT_DET_MAX_SIDE (the O(Q + T) solver state of a problem lives in 19 KB of LDS);
+ * above it GRIT_ERR_UNSUPPORTED.  An image with more than Tmax targets comes back unmatched.  Tmax >= 1 (pass 1 for an empty batch).
+ *
+ * grit_lsa_f32: the solver alone on a given cost [P, Q, ld] with counts [P] int32 = T of each problem (device memory); rows [P]
+ * int32 = the number of queries of each problem (<= Q; it uses the first rows[p] rows of its slab) or NULL = Q for all; match_t
+ * may be NULL.  Same device function, same bound.
+ *
+ * grit_det_loss_fwd_f32: one launch over logits [L, B, Q, K] and boxes [L, B, Q, 4]; no one-hot target exists anywhere: a row's
+ * class is read through match_t and tgt_labels.  out [L, GRIT_DET_LOSS_FIELDS] fp32, per layer:
+ *     [0] loss_ce           sum over ALL elements of the sigmoid focal loss (alpha, gamma = 2) / num_boxes
+ *                           (= the reference's sigmoid_focal_loss(...) * Q)
+ *     [1] loss_bbox         sum of the L1 distance of the matched pairs / num_boxes
+ *     [2] loss_giou         sum of 1 - GIoU of the matched pairs / num_boxes
+ *     [3] cardinality_error mean over images of | #{q: argmax_k logit != K - 1} - T |
+ *     [4] class_error       100 - 100 * (matched rows whose argmax is their label) / (matched rows); 100 with none
+ *     [5..]                 0
+ * num_boxes: ONE float in device memory, already all-reduced and clamped to >= 1 by the caller.  partials: [L * B * chunks, 8]
+ * float64 workspace, chunks = ceil(Q / GRIT_DET_LOSS_ROWS); ticket: one uint32 of workspace that belongs to this call alone, like
+ * partials (the entry point zeroes it on `stream` in front of the launch; the workgroup that takes the last ticket finalises).
+ *
+ * grit_det_loss_bwd_f32: one launch; writes EVERY element of dlogits [L, B, Q, K] and dboxes [L, B, Q, 4] (zero rows for unmatched
+ * queries).  coef [L, ldc] fp32 (ldc >= 3): the upstream gradients of out[l][0..2], i.e. the weights of the weighted loss sum;
+ * sigmoid is recomputed from the logits, nothing logits-sized is saved by the forward.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_DET_MAX_SIDE 512
+#define GRIT_DET_LOSS_ROWS 20
+#define GRIT_DET_LOSS_FIELDS 8
+int grit_det_match_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
+                       const int32_t* tgt_offsets, int L, int B, int Q, int K, int Tmax, float w_class, float w_bbox, float w_giou,
+                       float* cost, int ld, int32_t* match_q, int32_t* match_t, void* stream);
+int grit_lsa_f32(const float* cost, const int32_t* counts, const int32_t* rows, int P, int Q, int ld, int Tmax, int32_t* match_q,
+                 int32_t* match_t, void* stream);
+int grit_det_loss_fwd_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
+                          const int32_t* tgt_offsets, const int32_t* match_t, int L, int B, int Q, int K, float alpha,
+                          const float* num_boxes, double* partials, unsigned int* ticket, float* out, void* stream);
+int grit_det_loss_bwd_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
+                          const int32_t* tgt_offsets, const int32_t* match_t, int L, int B, int Q, int K, float alpha,
+                          const float* num_boxes, const float* coef, int ldc, float* dlogits, float* dboxes, void* stream);
 
 #ifdef __cplusplus
 }

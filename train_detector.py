@@ -1,0 +1,74 @@
+"""Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
+
+    python train_detector.py --synthetic --steps 3 [--batch-size 2] [--size 224] [key=value ...]
+
+The Visual Genome / LMDB readers, the hook-based solver and the COCO-style evaluation are out of scope of this build, so the only
+data source here is `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
+(grit_amd/models/detection/od_losses.py) and engine.det_engine.train_step, and prints the loss dictionary of every step.
+Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
+"""
+import argparse
+
+import torch
+
+from grit_amd.config import detection_config
+from engine.det_engine import train_step
+from models.detection.detector import build_detector
+from utils.misc import NestedTensor
+
+
+def synthetic_batch(generator, batch_size, size, num_classes, max_targets, device):
+    """Images ~ N(0, 1) and, per image, 1..max_targets boxes (cxcywh inside the unit square) with uniform labels."""
+    images = torch.randn(batch_size, 3, size, size, generator=generator)
+    mask = torch.zeros(batch_size, size, size, dtype=torch.bool)
+    targets = []
+    for _ in range(batch_size):
+        n = int(torch.randint(1, max_targets + 1, (1,), generator=generator))
+        wh = 0.05 + 0.4 * torch.rand(n, 2, generator=generator)
+        centre = wh / 2 + (1 - wh) * torch.rand(n, 2, generator=generator)
+        targets.append({'labels': torch.randint(0, num_classes, (n,), generator=generator).to(device),
+                        'boxes': torch.cat([centre, wh], 1).to(device)})
+    return NestedTensor(images.to(device), mask.to(device), any_padding=False), targets
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--synthetic', action='store_true', help='seeded random images and targets (the only data source of this build)')
+    ap.add_argument('--steps', type=int, default=3)
+    ap.add_argument('--batch-size', type=int, default=None)
+    ap.add_argument('--size', type=int, default=224, help='image side')
+    ap.add_argument('--max-targets', type=int, default=30)
+    ap.add_argument('overrides', nargs='*', help='dotted key=value configuration overrides')
+    args = ap.parse_args()
+    if not args.synthetic:
+        ap.error("only --synthetic is available: the Visual Genome readers are not part of this build")
+    over = {'model.backbone.pre_trained': 'none'}
+    for item in args.overrides:
+        key, _, value = item.partition('=')
+        try:
+            value = int(value)
+        except ValueError:
+            try:
+                value = float(value)
+            except ValueError:
+                value = {'true': True, 'false': False}.get(value.lower(), value)
+        over[key] = value
+    config = detection_config(**over)
+    torch.manual_seed(config.exp.seed)
+    device = torch.device('cuda')
+    model, criterion, _ = build_detector(config)
+    model.to(device)
+    backbone = [p for n, p in model.named_parameters() if n.startswith('backbone.') and p.requires_grad]
+    rest = [p for n, p in model.named_parameters() if not n.startswith('backbone.') and p.requires_grad]
+    optimizer = torch.optim.AdamW([{'params': rest, 'lr': config.optimizer.lr}, {'params': backbone, 'lr': config.optimizer.lr_backbone}],
+                                  weight_decay=config.optimizer.weight_decay)
+    g = torch.Generator().manual_seed(config.exp.seed)
+    batch_size = args.batch_size or config.optimizer.batch_size
+    for step in range(args.steps):
+        samples, targets = synthetic_batch(g, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
+        total, losses = train_step(model, criterion, optimizer, samples, targets, config.optimizer.clip_max_norm)
+        print('step %d  loss %.5f  %s' % (step, float(total), {k: round(float(v), 5) for k, v in sorted(losses.items())}))
+
+
+if __name__ == '__main__':
+    main()
