@@ -193,7 +193,7 @@ class BucketedDataParallel(nn.Module):
         parameters without a gradient are zeroed (the flat buffer still holds the previous step's values there)."""
         if b.packed:
             return
-        _linear_ops.wait_deferred()  # small-map weight gradients computed beside the backward chain (grit_amd/ops/linear.py)
+        _linear_ops.flush_deferred()  # the deferred weight gradients and reductions are computed now (grit_amd/ops/linear.py)
         src, dst, stale = [], [], []
         for p, view in zip(b.params, b.views):
             if p.grad is None:

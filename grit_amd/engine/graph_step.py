@@ -116,9 +116,7 @@ def abandon_capture(model, opts, iteration=None):
     gradient slots, packed flags, iteration count) describe a pass that never ran; the optimizers would keep reading their
     per-step scalars from the device table.  The next step then runs as an ordinary eager step."""
     from grit_amd.ops import linear as _linear
-    _linear.abandon_deferred()
-    _linear._deferral["active"] = False
-    _linear._deferral["pending"].clear()
+    _linear.abandon_scope()
     ddp = model.ddp
     for b in ddp.buckets:
         b.work = b.wire = None

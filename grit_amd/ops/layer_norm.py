@@ -13,8 +13,8 @@ from torch.autograd.function import once_differentiable
 
 from grit_amd import lib as _lib
 from grit_amd.ops import backend
-from grit_amd.ops.linear import (SlabGroup, _own_input_grad, _own_linear, defer_slab_group, defer_weight_bias_grad, finish_group, fork, join, on_stream, single_use_now,
-                                 slab_sum)
+from grit_amd.ops.linear import (SlabGroup, _own_linear, _rows, defer_slab_group, defer_weight_bias_grad, projection_input_grad,
+                                 single_use_now, slab_sum, weight_grad)
 from grit_amd.ops.profiling import gemm_work, timed
 
 SUPPORTED_C = (128, 256, 512, 1024, 2048, 4096)
@@ -221,8 +221,7 @@ def _residual_linear(inp, lin_w, lin_b, s2, scale, rows_per_sample):
     if not (inp.is_cuda and inp.dtype == torch.bfloat16 and s2.dtype == torch.bfloat16 and inp.numel() // inp.shape[-1] >= 8192):
         return None
     from grit_amd.ops import gemm as _gemm
-    x2 = inp.reshape(-1, inp.shape[-1])
-    return _gemm.long_linear_residual(x2 if x2.is_contiguous() else x2.contiguous(), lin_w, lin_b, s2, scale, rows_per_sample)
+    return _gemm.long_linear_residual(_rows(inp), lin_w, lin_b, s2, scale, rows_per_sample)
 
 
 def _projection_input_grad(ctx, d_branch, inp, lin_w):
@@ -240,11 +239,7 @@ def _projection_input_grad(ctx, d_branch, inp, lin_w):
         with timed("gemm_lib", **gemm_work(d_branch.shape[0], lin_w.shape[1], lin_w.shape[0])):
             d = torch.mm(d_branch, lin_w)  # (no transposed copy of the weight at hand: the library's product, then the mask -- the contract holds)
         return relu_dropout_backward(inp2, d, h["p"], h["seed"]).view(inp.shape)
-    d_inp = _own_input_grad(d_branch, ctx.lin_w_obj, inp.shape)
-    if d_inp is None:
-        with timed("gemm_lib", **gemm_work(d_branch.shape[0], lin_w.shape[1], lin_w.shape[0])):
-            d_inp = torch.mm(d_branch, lin_w).view(inp.shape)
-    return d_inp
+    return projection_input_grad(d_branch, ctx.lin_w_obj, lin_w, inp.shape)
 
 
 class _LinearAddLayerNormFn(Function):
@@ -256,7 +251,6 @@ class _LinearAddLayerNormFn(Function):
     def forward(ctx, inp, lin_w, lin_b, shortcut, scale, weight, bias, eps, drop_p, seed_dev, single_use=False):
         ctx.single_use = single_use
         ctx.sum_params = (weight, bias, lin_b) if single_use else None  # the parameters whose gradients the node's sums are
-        ctx.lin_w_param = lin_w if single_use else None
         ctx.lin_w_obj = lin_w  # the tensor object of the call: transposed copies are attached to it (grit_amd/ops/transposed.py)
         C = shortcut.shape[-1]
         s2 = shortcut.reshape(-1, C)
@@ -304,14 +298,11 @@ class _LinearAddLayerNormFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gx, gy):
-        from grit_amd.ops.linear import weight_grad
         x2, weight, mean, rstd, scale, inp, lin_w, seed_dev = ctx.saved_tensors
         group = SlabGroup()  # LayerNorm sums + the projection's weight gradient: one reduction launch for the node
         dx, d_branch, sums = _add_layer_norm_backward(x2, weight, mean, rstd, scale, gx, gy, ctx.shape[0], True, ctx.drop_p,
                                                       seed_dev, group)
-        inp2 = inp.reshape(-1, inp.shape[-1])
-        if not inp2.is_contiguous():
-            inp2 = inp2.contiguous()
+        inp2 = _rows(inp)
         d_inp = d_lin_w = None
         # drop path: d_branch = scale[b] * dx is exactly zero in the rows of dropped samples -- the projection's weight gradient skips them
         rs = (scale, d_branch.shape[0] // ctx.shape[0]) if (scale is not None and ctx.drop_p == 0) else None
@@ -327,23 +318,11 @@ class _LinearAddLayerNormFn(Function):
                 d_inp = _projection_input_grad(ctx, d_branch, inp, lin_w)
             return (d_inp, deferred[0], sums[2].to(lin_w.dtype), dx.view(ctx.shape), None, sums[0], sums[1], None, None, None,
                     None)
-        # small maps inside a deferral scope: the projection's weight gradient beside the chain (grit_amd/ops/linear.py fork)
-        side = fork(d_branch, inp2, rows=d_branch.shape[0], single_use=ctx.single_use) \
-            if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
-        if side is not None and getattr(side, "deferred", False):
-            group.run()  # the LayerNorm sums stay on this stream; the weight gradient of a small map has no partials (S = 1)
-            with on_stream(side):
-                d_lin_w = weight_grad(d_branch, inp2)
         if ctx.needs_input_grad[0]:
             d_inp = _projection_input_grad(ctx, d_branch, inp, lin_w)
-        if d_lin_w is None:
-            d_lin_w = weight_grad(d_branch, inp2, group, param=lin_w, row_scale=rs) if ctx.needs_input_grad[1] else None
-            sp = ctx.sum_params
-            # long maps: the node's reductions (weight-gradient partials, LayerNorm / bias sums) join the scope's grouped launch
-            finish_group(group, side is None and sp is not None and sums.dtype == lin_w.dtype and ctx.needs_input_grad[2]
-                         and ctx.needs_input_grad[5] and ctx.needs_input_grad[6],
-                         [] if sp is None else [(ctx.lin_w_param, d_lin_w), (sp[0], sums[0]), (sp[1], sums[1]), (sp[2], sums[2])])
-        join(side, d_lin_w)
+        if ctx.needs_input_grad[1]:
+            d_lin_w = weight_grad(d_branch, inp2, group, param=lin_w, row_scale=rs)
+        group.run()  # weight-gradient partials and LayerNorm / bias sums right behind their kernels (still in the Infinity Cache)
         return d_inp, d_lin_w, sums[2].to(lin_w.dtype), dx.view(ctx.shape), None, sums[0], sums[1], None, None, None, None
 
 

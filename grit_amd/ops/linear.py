@@ -9,6 +9,7 @@ batched GEMM with fp32 partials (bmm, out_dtype = float32) followed by a sum ove
 column-sum kernel (grit_colsum).  Used for the four Linears of every Swin block and MSDeformAttn.value_proj."""
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -22,31 +23,17 @@ from grit_amd.ops.profiling import gemm_work, timed
 
 MIN_ROWS = int(os.environ.get("GRIT_LINEAR_MIN_ROWS", "512"))  # below this the launch overhead dominates: leave it to torch
 
-# The weight / bias gradients are not on the critical path of backward (nothing downstream of the node reads them), the input
-# gradient is.  With GRIT_WGRAD_STREAM=1 they are enqueued on a second HIP stream and the input-gradient GEMM on the current
-# one, so that the two GEMMs could fill each other's partial last wave of tiles and the small slab-sum / column-sum launches
-# run beside a GEMM instead of between two.  MEASURED SLOWER (64.4 -> 69.3 ms/step, profiles/r02/negative_results.txt): two
-# 128-KB-LDS GEMMs sharing the chip evict each other's L2 working set; the knob stays for A/B runs, default off.
-# (round 6, same-box A/B inside the captured step, profiles/r06/ab_wgrad_stream.txt: 47.5 -> 48.5 ms; with the join deferred to the bucket
-# pack -- the weight gradients beside the HBM-bound LayerNorm / window-attention kernels that follow -- 48.2 ms: matrix work and HBM
-# streaming do not overlap on this chip, they add up to ~80 % of their sum, tools/micro/overlap_probe.py)
-WGRAD_STREAM = os.environ.get("GRIT_WGRAD_STREAM", "0") == "1"
-_side_streams = {}
-
-
-# Small maps (the two decoders and the grid net: 640 .. 4 800 rows) are another matter: their GEMMs fill a few dozen CUs for
-# 10-30 us each and the backward pass is one long dependent chain of them, so the weight / bias gradients -- nothing downstream
-# in backward reads them -- can run BESIDE the chain on a second stream.  MEASURED SLOWER in the benchmark step (65.0 -> 65.7 ms,
-# two alternating passes on one box, profiles/r03/negative_results.txt): that part of the step is bound by how fast the host
-# enqueues its tiny kernels, and every fork adds two cross-stream event operations.  GRIT_WGRAD_STREAM_SMALL=1 (default 0) enables
-# it for nodes with fewer than SMALL_ROWS rows, and only while a gradient-bucket wrapper has declared a deferral scope
-# (grit_amd.ddp: begin_deferral in forward, wait_deferred before it packs or hands out gradients): the main stream then does not
-# wait for the side stream at the end of the node but when the gradients are first consumed.  A parameter used twice in one
-# forward pass would have its two gradients added by autograd on the main stream before that point, so the deferral is opt-in
-# per call site (`single_use=True`: the caller guarantees the weight receives exactly one gradient per backward pass).
-WGRAD_STREAM_SMALL = os.environ.get("GRIT_WGRAD_STREAM_SMALL", "0") == "1"
-SMALL_ROWS = int(os.environ.get("GRIT_WGRAD_SMALL_ROWS", "16384"))
-_deferral = {"active": False, "pending": set()}
+# Built, measured slower or neutral on every workload, and removed together with their options -- do not build them a third time:
+#  - weight / bias gradients on a second HIP stream beside the input-gradient GEMM.  Long maps: two 128-KB-LDS GEMMs sharing the chip
+#    evict each other's L2 working set, and matrix work beside HBM streaming adds up to ~80 % of their sum (64.4 -> 69.3 ms,
+#    profiles/r02/negative_results.txt; 47.5 -> 48.5 ms inside the captured step, profiles/r06/ab_wgrad_stream.txt).  Short maps, with
+#    the join left to the bucket pack: that part of the step is bound by how fast the host enqueues its tiny kernels, and every fork
+#    adds two cross-stream event operations (65.0 -> 65.7 ms, profiles/r03/negative_results.txt);
+#  - long-map weight gradients left to the bucket flush: fewer and fatter slices, but operands that were in the Infinity Cache when
+#    their node ran come back from HBM a bucket later (+0.45 ms, profiles/r03/negative_results.txt #14);
+#  - long-map reductions left to the flush: what the bigger launch saves, the colder fp32 partials cost (neutral,
+#    profiles/r03/negative_results.txt).
+_deferral = {"active": False}
 
 
 def mark_single_use(*modules):
@@ -86,10 +73,6 @@ def single_use_now(flag):
 # contiguous gradient), otherwise the parameter received a second gradient and the run stops with an error instead of training
 # on garbage.
 WGRAD_DEFER = os.environ.get("GRIT_WGRAD_DEFER", "1") != "0"
-# GRIT_WGRAD_DEFER_LONG=1 (default 0): the long maps' weight gradients too (where single-use).  Measured +0.45 ms
-# (profiles/r03/negative_results.txt #14): fewer and fatter slices, but operands that were in the Infinity Cache when their node ran
-# come back from HBM a bucket later.
-WGRAD_DEFER_LONG = os.environ.get("GRIT_WGRAD_DEFER_LONG", "0") == "1"
 _deferral["jobs"] = []
 _deferral["slabs"] = []
 # GRIT_WGRAD_PARK (default 1): a long-map weight gradient whose Linear is marked with park_weight_grad_for_partner (the attention
@@ -108,37 +91,71 @@ def park_weight_grad_for_partner(first, partner):
     partner.weight._grit_wgrad_pickup = True
 
 
+def _rows(t):
+    """t as [rows, last dimension], contiguous (a copy only where the view is not)."""
+    t2 = t.reshape(-1, t.shape[-1])
+    return t2 if t2.is_contiguous() else t2.contiguous()
+
+
+def _own_wgrad_operands(dy2, x2):
+    """The own weight-gradient kernels can read these two operands: bf16 on the device, unit inner stride, rows a multiple of 8
+    elements apart, 16-byte aligned.  (Row-count thresholds and divisibility rules differ per kernel: they stay with the callers.)"""
+    return (dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and dy2.stride(1) == 1 and x2.stride(1) == 1
+            and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0)
+
+
+class _Job(namedtuple("_Job", "dy x M N K row_scale weight bias w_check b_check w_out b_out", defaults=(None, None, 0, 0, 0, 0))):
+    """One weight (+ bias) gradient problem dW [N, K] = dy^T x, db [N] = colsum(dy).  A deferred or parked one also names where its
+    results belong: weight / bias are the parameters (bias None: no bias gradient wanted), w_check / b_check the device address each
+    parameter's .grad must have at flush time, w_out / b_out the address the result is written to -- the same, except for a row range
+    of a packed parameter, which lies inside the checked tensor.  Addresses only: autograd adopts a gradient tensor nobody else holds."""
+    __slots__ = ()
+
+    @property
+    def tiles(self):
+        """256 x 256 output tiles of the long-map kernel."""
+        return (self.N // 256) * (self.K // 256)
+
+    @property
+    def max_slices(self):
+        """The most row slices the long-map kernel should take: loops of >= 16 steps of 32 rows."""
+        return max(1, (self.M // 32) // 16)
+
+    def fill(self, splits, dw_partial, db_partial):
+        """The kernels' job record for `splits` row slices whose fp32 partials go to the two device addresses (db_partial None: none)."""
+        return _lib.WgradJob(self.dy.data_ptr(), self.dy.stride(0), self.x.data_ptr(), self.x.stride(0), self.M, self.N, self.K, splits,
+                             dw_partial, db_partial, *_rows_arg(self.row_scale, self.M))
+
+
+def _job(dy2, x2, row_scale=None, **where):
+    return _Job(dy2, x2, dy2.shape[0], dy2.shape[1], x2.shape[1], row_scale, **where)
+
+
 def defer_weight_bias_grad(dy2, x2, weight, bias, need_dw, need_db, single_use, row_scale=None):
     """(dW, db) as empty tensors that flush_deferred() will fill, or None when the job must be done by the node itself."""
-    if not (WGRAD_DEFER and single_use and need_dw and _deferral["active"] and dy2.is_cuda and dy2.dtype == torch.bfloat16
-            and x2.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.grad is None
+    if not (WGRAD_DEFER and single_use and need_dw and _deferral["active"] and _own_wgrad_operands(dy2, x2)
+            and weight.dtype == torch.bfloat16 and weight.grad is None
             and (not need_db or (bias is not None and bias.grad is None and bias.dtype == torch.bfloat16))
             and not backend.foreign_capture()):
         return None
     M, N = dy2.shape
     K = x2.shape[1]
-    # short maps always; long maps (the Swin blocks) when the long-map kernel takes the shape: the ten or so weight gradients a
-    # gradient bucket collects then run as ONE launch of ~256 workgroups with 800-step loops and TWO row slices each instead of ten
-    # launches with 16-64 slices -- the fp32 slices (3.9 GB per step written and read back) shrink by an order of magnitude
-    long_ok = (WGRAD_DEFER_LONG and WGRAD_TN_GROUPED and M >= WGRAD_SMALL_MAX_ROWS
-               and _lib.load().grit_wgrad_tn_group_ok(M, N, K) == 1)
-    park = (WGRAD_PARK and WGRAD_TN and WGRAD_TN_GROUPED and not long_ok and not need_db and M >= WGRAD_SMALL_MAX_ROWS
-            and getattr(weight, "_grit_wgrad_park", False) and _lib.load().grit_wgrad_tn_group_ok(M, N, K) == 1)
-    long_ok = long_ok or park
-    if not ((M < WGRAD_SMALL_MAX_ROWS or long_ok) and N % 64 == 0 and K % 64 == 0 and dy2.stride(1) == 1 and x2.stride(1) == 1
-            and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):
+    # short maps always; a long map only to be parked for its partner's launch
+    parked = (WGRAD_PARK and WGRAD_TN and WGRAD_TN_GROUPED and not need_db and M >= WGRAD_SMALL_MAX_ROWS
+              and getattr(weight, "_grit_wgrad_park", False) and _lib.load().grit_wgrad_tn_group_ok(M, N, K) == 1)
+    if not ((M < WGRAD_SMALL_MAX_ROWS or parked) and N % 64 == 0 and K % 64 == 0):
         return None
     # straight into the gradient bucket (round 5: the short maps' gradients too -- ~60 M decoder parameters were copied into their slots
     # by the bucket pack, 12 multi-tensor launches of ~19 us per step; GRIT_DEFER_SLOT_SHORT=0 restores the copies)
-    dw = grad_slot(weight, torch.bfloat16, dy2.device) if (long_ok or DEFER_SLOT_SHORT) else None
+    dw = grad_slot(weight, torch.bfloat16, dy2.device) if (parked or DEFER_SLOT_SHORT) else None
     if dw is None:
         dw = torch.empty((N, K), dtype=torch.bfloat16, device=dy2.device)
     db = (grad_slot(bias, torch.bfloat16, dy2.device) if DEFER_SLOT_SHORT else None) if need_db else None
     if need_db and db is None:
         db = torch.empty((N,), dtype=torch.bfloat16, device=dy2.device)
-    # no reference to dw / db is kept (autograd only adopts a gradient tensor nobody else holds): addresses only
-    _deferral["parked" if park else "jobs"].append((dy2, x2, weight, bias if need_db else None, dw.data_ptr(),
-                                                    db.data_ptr() if need_db else 0, M, N, K, row_scale))
+    pw, pb = dw.data_ptr(), db.data_ptr() if need_db else 0
+    _deferral["parked" if parked else "jobs"].append(_job(dy2, x2, row_scale, weight=weight, bias=bias if need_db else None,
+                                                          w_check=pw, b_check=pb, w_out=pw, b_out=pb))
     return dw, db
 
 
@@ -153,9 +170,7 @@ def defer_packed_weight_bias_grad(parts, weight, bias):
     K = weight.shape[1]
     for dy2, x2 in parts:
         M, N = dy2.shape
-        if not (dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and M < WGRAD_SMALL_MAX_ROWS and N % 64 == 0
-                and K % 64 == 0 and x2.shape == (M, K) and dy2.stride(1) == 1 and x2.stride(1) == 1 and dy2.stride(0) % 8 == 0
-                and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):
+        if not (_own_wgrad_operands(dy2, x2) and M < WGRAD_SMALL_MAX_ROWS and N % 64 == 0 and K % 64 == 0 and x2.shape == (M, K)):
             return None
     if sum(dy2.shape[1] for dy2, _ in parts) != weight.shape[0]:
         return None
@@ -168,9 +183,9 @@ def defer_packed_weight_bias_grad(parts, weight, bias):
         db = torch.empty(tuple(bias.shape), dtype=torch.bfloat16, device=dev)
     pw0, pb0, row = dw.data_ptr(), db.data_ptr(), 0
     for dy2, x2 in parts:
-        M, N = dy2.shape
-        _deferral["jobs"].append((dy2, x2, (weight, pw0), (bias, pb0), pw0 + row * K * 2, pb0 + row * 2, M, N, K, None))
-        row += N
+        _deferral["jobs"].append(_job(dy2, x2, weight=weight, bias=bias, w_check=pw0, b_check=pb0,
+                                      w_out=pw0 + row * K * 2, b_out=pb0 + row * 2))
+        row += dy2.shape[1]
     return dw, db
 
 
@@ -212,12 +227,7 @@ class _PackedInProjFn(Function):
     def backward(ctx, dqk, dv):
         qk_in, v_in, weight = ctx.saved_tensors
         E = weight.shape[1]
-        dqk2, dv2 = dqk.reshape(-1, 2 * E), dv.reshape(-1, E)
-        dqk2 = dqk2 if dqk2.is_contiguous() else dqk2.contiguous()
-        dv2 = dv2 if dv2.is_contiguous() else dv2.contiguous()
-        q2, v2 = qk_in.reshape(-1, E), v_in.reshape(-1, E)
-        q2 = q2 if q2.is_contiguous() else q2.contiguous()
-        v2 = v2 if v2.is_contiguous() else v2.contiguous()
+        dqk2, dv2, q2, v2 = _rows(dqk), _rows(dv), _rows(qk_in), _rows(v_in)  # [.., 2E], [.., E], [.., E], [.., E]
         d_qk_in = d_v_in = dw = db = None
         wt = _short_transposed(ctx.weight_param, dqk2)  # [E, 3E] = W^T, or None: no copy / outside the short-map policy
         if wt is not None:
@@ -284,8 +294,6 @@ def _verify(p, ptr, what, final):
     hook, i.e. possibly BETWEEN the deliveries of two gradients of one node: a gradient the engine has not delivered yet (it
     holds the tensor, the memory is valid) is written anyway and checked at the next flush -- before anything can have replaced
     it, because every bucket pack starts with a flush -- and at the final flush (backward is over) it must be there."""
-    if isinstance(p, tuple):  # (parameter, address its gradient must have): a job that fills a ROW RANGE of a packed parameter's gradient
-        p, ptr = p
     if p.grad is None and not final:
         _deferral["unverified"].append((p, ptr, what))
     elif p.grad is None or p.grad.data_ptr() != ptr:
@@ -296,25 +304,6 @@ def _verify_earlier(final):
     earlier, _deferral["unverified"] = _deferral["unverified"], []
     for p, ptr, what in earlier:
         _verify(p, ptr, what, final)
-
-
-# GRIT_SLAB_DEFER_LONG=1 (default 0): also the LONG-map nodes (Swin blocks) leave their reductions to the scope's flush.  Measured
-# neutral (59.26 / 59.23 -> 59.43 / 59.10 ms, profiles/r03/negative_results.txt): summed right behind the GEMM the fp32 partials
-# are still in the Infinity Cache, summed a bucket later they come from HBM -- what the bigger launch saves, the colder data costs.
-FINISH_DEFER = os.environ.get("GRIT_SLAB_DEFER_LONG", "0") == "1"
-
-
-def finish_group(group, single_use, outputs):
-    """End of a backward node that owns a SlabGroup.  outputs: [(parameter, gradient tensor the group's launch will fill)].  Inside a
-    deferral scope, when every one of them belongs to a parameter declared single-use that holds no gradient yet, the launch is
-    left to the scope's flush (one grouped launch for the nodes of a whole gradient bucket instead of one small launch per node:
-    the long-map weight-gradient partials are then summed at streaming bandwidth); otherwise it runs now."""
-    if group is None or not group.jobs:
-        return
-    checks = [(p, t.data_ptr()) for p, t in outputs if t is not None]
-    if FINISH_DEFER and single_use and checks and all(p is not None for p, _ in checks) and defer_slab_group(group, checks):
-        return
-    group.run()
 
 
 def _flush_deferred_slabs(into=None, final=False):
@@ -333,9 +322,46 @@ def _flush_deferred_slabs(into=None, final=False):
         group.run()
 
 
+def _launch_grouped(kind, jobs, splits, dw_partials, db_partials):
+    """One grouped weight-gradient launch -- grit_wgrad_tn_grouped (kind "tn": 256 x 256 tiles) or grit_wgrad_small_grouped ("small") --
+    over `jobs`: per job its row slices and the device addresses of its fp32 partials (bias: None for none), with the profiler's
+    accounting."""
+    lib = _lib.load()
+    table = (_lib.WgradJob * len(jobs))(*[j.fill(S, pw, pb) for j, S, pw, pb in zip(jobs, splits, dw_partials, db_partials)])
+    launch, name, family = (lib.grit_wgrad_tn_grouped, "grit_wgrad_tn_grouped", "wgrad_tn") if kind == "tn" else \
+        (lib.grit_wgrad_small_grouped, "grit_wgrad_small_grouped", "wgrad_small")
+    flops = 2.0 * sum(j.M * j.N * j.K for j in jobs)
+    nbytes = sum(2.0 * j.M * (j.N + j.K) + 4.0 * S * j.N * j.K for j, S in zip(jobs, splits))  # operands once + the fp32 slices written
+    with _lib.device_guard(jobs[0].dy.device), timed("gemm_own", flops=flops, kernel=family, bytes=nbytes):
+        st = launch(table, len(jobs), _lib.current_stream_ptr())
+    _lib.check(st, name)
+
+
+def _chunk_layout(kind, chunk):
+    """([(row slices, bias slabs, offset of the weight partials, offset of the bias partials)] per job of a chunk, workspace size),
+    offsets and size in fp32 elements."""
+    if kind == "tn":
+        best, best_fill = 1, 0.0
+        for cand in range(1, 9):  # row slices per problem: the fullest last round of workgroups, loops of >= 16 steps
+            wgs = sum(j.tiles * min(cand, j.max_slices) for j in chunk)
+            fill = wgs / (-(-wgs // 256) * 256.0)
+            if fill > best_fill + 0.02:
+                best, best_fill = cand, fill
+        splits = [tn_slices(j.M, min(best, j.max_slices)) for j in chunk]
+        slabs = splits if WGRAD_TN_BIAS else [max(1, min(256, j.M // 64)) for j in chunk]  # bias: by-product per slice
+    else:
+        splits = slabs = [_lib.load().grit_wgrad_group_splits(j.M) for j in chunk]
+    layout, total = [], 0
+    for j, S, sl in zip(chunk, splits, slabs):
+        layout.append((S, sl, total, total + S * j.N * j.K))
+        total += S * j.N * j.K + (sl * j.N if j.bias is not None else 0)
+    return layout, total
+
+
 def flush_deferred(final=False):
     """Compute every deferred weight / bias gradient (one grouped GEMM launch + one grouped reduction per <= 32 problems) and
-    every deferred reduction.  final: backward is over (finish_gradient_sync), every gradient must have been delivered."""
+    every deferred reduction: call before anything reads parameter gradients.  final: backward is over (finish_gradient_sync),
+    every gradient must have been delivered."""
     _verify_earlier(final)
     jobs = _deferral["jobs"] + _deferral["parked"]  # parked jobs whose partner never came (a bucket boundary, a frozen partner)
     if not jobs:
@@ -343,66 +369,40 @@ def flush_deferred(final=False):
         return
     _deferral["jobs"], _deferral["parked"] = [], []
     lib = _lib.load()
-    dev = jobs[0][0].device
-    for dy2, x2, w, b, pw, pb, M, N, K, _rs in jobs:
-        _verify(w, pw, "weight gradient [%d, %d]" % (N, K), final)
-        if b is not None:
-            _verify(b, pb, "bias gradient [%d]" % N, final)
+    dev = jobs[0].dy.device
+    for j in jobs:
+        _verify(j.weight, j.w_check, "weight gradient [%d, %d]" % (j.N, j.K), final)
+        if j.bias is not None:
+            _verify(j.bias, j.b_check, "bias gradient [%d]" % j.N, final)
     # problems the long-map kernel takes (256 x 256 tiles) go through it TOGETHER: one of them alone is four tiles, thirty of them
     # are a launch of 256 workgroups with 75-step loops (1 PFLOP/s instead of the L2-bound 0.26 of the 64 x 64-tile kernel)
-    big = [j for j in jobs if WGRAD_TN_GROUPED and lib.grit_wgrad_tn_group_ok(j[6], j[7], j[8])]
-    small = [j for j in jobs if not (WGRAD_TN_GROUPED and lib.grit_wgrad_tn_group_ok(j[6], j[7], j[8]))]
-    longs = [j for j in big if j[6] >= WGRAD_SMALL_MAX_ROWS]  # their own launches: a workgroup of theirs runs ~10x longer
-    big = [j for j in big if j[6] < WGRAD_SMALL_MAX_ROWS]
-    chunks = [("tn", longs[i:i + _lib.WGRAD_GROUP_MAX]) for i in range(0, len(longs), _lib.WGRAD_GROUP_MAX)]
-    chunks += [("tn", big[i:i + _lib.WGRAD_GROUP_MAX]) for i in range(0, len(big), _lib.WGRAD_GROUP_MAX)]
-    chunks += [("small", small[i:i + _lib.WGRAD_GROUP_MAX]) for i in range(0, len(small), _lib.WGRAD_GROUP_MAX)]
+    fits = [bool(WGRAD_TN_GROUPED and lib.grit_wgrad_tn_group_ok(j.M, j.N, j.K)) for j in jobs]
+    longs = [j for j, f in zip(jobs, fits) if f and j.M >= WGRAD_SMALL_MAX_ROWS]  # their own launches: a workgroup of theirs runs ~10x longer
+    big = [j for j, f in zip(jobs, fits) if f and j.M < WGRAD_SMALL_MAX_ROWS]
+    small = [j for j, f in zip(jobs, fits) if not f]
+    chunks = [(kind, some[i:i + _lib.WGRAD_GROUP_MAX]) for kind, some in (("tn", longs), ("tn", big), ("small", small))
+              for i in range(0, len(some), _lib.WGRAD_GROUP_MAX)]
     with _lib.device_guard(dev):
         for ci, (kind, chunk) in enumerate(chunks):
-            if kind == "tn":
-                tiles = sum((j[7] // 256) * (j[8] // 256) for j in chunk)
-                best, best_fill = 1, 0.0
-                for cand in range(1, 9):  # row slices per problem: the fullest last round of workgroups, loops of >= 16 steps
-                    wgs = sum((j[7] // 256) * (j[8] // 256) * max(1, min(cand, (j[6] // 32) // 16)) for j in chunk)
-                    fill = wgs / (-(-wgs // 256) * 256.0)
-                    if fill > best_fill + 0.02:
-                        best, best_fill = cand, fill
-                splits = [tn_slices(j[6], max(1, min(best, (j[6] // 32) // 16))) for j in chunk]
-                slabs = splits if WGRAD_TN_BIAS else [max(1, min(256, j[6] // 64)) for j in chunk]  # bias: by-product per slice
-            else:
-                splits = [lib.grit_wgrad_group_splits(j[6]) for j in chunk]
-                slabs = splits
-            sizes, total = [], 0
-            for job, S, sl in zip(chunk, splits, slabs):
-                dy2, x2, w, b, pw, pb, M, N, K, _rs = job
-                sizes.append((S, sl, total, total + S * N * K))
-                total += S * N * K + (sl * N if b is not None else 0)
+            layout, total = _chunk_layout(kind, chunk)
             work = torch.empty(total, dtype=torch.float32, device=dev)
             base = work.data_ptr()
-            table = (_lib.WgradJob * len(chunk))()
-            ctable = (_lib.ColsumJob * len(chunk))()
-            nc = 0
+            bias_in_launch = kind == "small" or WGRAD_TN_BIAS  # else the long-map kernel leaves the bias gradients to a grouped column sum
+            dw_partials, db_partials, colsums = [], [], []
             group = SlabGroup()
-            for t, (job, (S, sl, woff, boff)) in enumerate(zip(chunk, sizes)):
-                dy2, x2, w, b, pw, pb, M, N, K, rs = job
-                bias_here = (base + 4 * boff) if b is not None else None
-                table[t] = _lib.WgradJob(dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), M, N, K, S, base + 4 * woff,
-                                         None if (kind == "tn" and not WGRAD_TN_BIAS) else bias_here, *_rows_arg(rs, M))
-                if kind == "tn" and b is not None and not WGRAD_TN_BIAS:
-                    ctable[nc] = _lib.ColsumJob(dy2.data_ptr(), dy2.stride(0), M, N, sl, bias_here)
-                    nc += 1
-                group.add_raw(work[woff:], 1, 0, S, N * K, pw, True)
-                if b is not None:
-                    group.add_raw(work[boff:], 1, 0, sl, N, pb, True)
-            with timed("gemm_own", flops=2.0 * sum(j[6] * j[7] * j[8] for j in chunk), kernel="wgrad_tn" if kind == "tn" else "wgrad_small",
-                       bytes=sum(2.0 * j[6] * (j[7] + j[8]) + 4.0 * S * j[7] * j[8] for j, S in zip(chunk, splits))):
-                if kind == "tn":
-                    st = lib.grit_wgrad_tn_grouped(table, len(chunk), _lib.current_stream_ptr())
-                else:
-                    st = lib.grit_wgrad_small_grouped(table, len(chunk), _lib.current_stream_ptr())
-            _lib.check(st, "grit_wgrad_tn_grouped" if kind == "tn" else "grit_wgrad_small_grouped")
-            if nc:
-                _lib.check(lib.grit_colsum_grouped(ctable, nc, _lib.current_stream_ptr()), "grit_colsum_grouped")
+            for j, (S, sl, woff, boff) in zip(chunk, layout):
+                bias_here = (base + 4 * boff) if j.bias is not None else None
+                dw_partials.append(base + 4 * woff)
+                db_partials.append(bias_here if bias_in_launch else None)
+                if bias_here is not None and not bias_in_launch:
+                    colsums.append(_lib.ColsumJob(j.dy.data_ptr(), j.dy.stride(0), j.M, j.N, sl, bias_here))
+                group.add_raw(work[woff:], 1, 0, S, j.N * j.K, j.w_out, True)
+                if j.bias is not None:
+                    group.add_raw(work[boff:], 1, 0, sl, j.N, j.b_out, True)
+            _launch_grouped(kind, chunk, [S for S, _, _, _ in layout], dw_partials, db_partials)
+            if colsums:
+                ctable = (_lib.ColsumJob * len(colsums))(*colsums)
+                _lib.check(lib.grit_colsum_grouped(ctable, len(colsums), _lib.current_stream_ptr()), "grit_colsum_grouped")
             if ci == len(chunks) - 1:
                 _flush_deferred_slabs(into=group, final=final)  # the nodes' own deferred reductions ride in the last chunk's launch
             group.run()  # keeps `work` (and through `chunk` the operands) alive until the launches are enqueued
@@ -420,8 +420,7 @@ def begin_deferral(owner=None):
 def close_deferral(owner=None):
     """A forward pass of `owner` that records no graph: whatever scope it had open is over (nothing will flush it)."""
     if _deferral["active"] and _deferral.get("owner") is owner:
-        abandon_deferred()
-        _deferral["active"] = False
+        abandon_scope()
 
 
 def abandon_deferred():
@@ -429,71 +428,17 @@ def abandon_deferred():
     _deferral["jobs"], _deferral["slabs"], _deferral["unverified"], _deferral["parked"] = [], [], [], []
 
 
-def wait_deferred(final=False):
-    """Deferred weight gradients are computed now, and the current stream waits for every side stream that still runs
-    weight-gradient work: call before anything reads parameter gradients."""
-    flush_deferred(final)
-    for side in _deferral["pending"]:
-        torch.cuda.current_stream(side.device).wait_stream(side)
-    _deferral["pending"].clear()
+def abandon_scope():
+    """Forget every pending job and close the scope: nothing of the pass that opened it will be flushed."""
+    abandon_deferred()
+    _deferral["active"] = False
 
 
 def end_deferral():
     try:
-        wait_deferred(final=True)
+        flush_deferred(final=True)
     finally:
         _deferral["active"] = False
-
-
-def fork(*inputs, rows=None, single_use=False):
-    """Side stream ordered after everything enqueued so far on the current stream (None when the knob is off / on CPU).
-    `inputs` are the tensors the side work reads: their memory is not handed out again before that work has run.
-    rows / single_use: the small-map deferral described above."""
-    if not (inputs and inputs[0].is_cuda):
-        return None
-    small = (WGRAD_STREAM_SMALL and single_use and rows is not None and rows < SMALL_ROWS and _deferral["active"]
-             and not backend.foreign_capture())
-    if not (WGRAD_STREAM or small):
-        return None
-    dev = inputs[0].device
-    side = _side_streams.get(dev)
-    if side is None:
-        side = _side_streams[dev] = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    for t in inputs:
-        t.record_stream(side)
-    side.deferred = bool(small and not WGRAD_STREAM)
-    return side
-
-
-def join(side, *outputs):
-    """The current stream waits for the side work; `outputs` (allocated on the side stream) are consumed on the current one.
-    In a deferral scope (small maps) the wait is left to wait_deferred()."""
-    if side is None:
-        return
-    main = torch.cuda.current_stream(side.device)
-    for t in outputs:
-        if t is not None:
-            t.record_stream(main)
-    if getattr(side, "deferred", False):
-        _deferral["pending"].add(side)
-        return
-    main.wait_stream(side)
-
-
-class on_stream:
-    """`with on_stream(side):` -- torch.cuda.stream(side), or nothing when side is None."""
-
-    def __init__(self, side):
-        self.ctx = torch.cuda.stream(side) if side is not None else None
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
 
 
 GRAD_IN_PLACE = os.environ.get("GRIT_GRAD_IN_PLACE", "1") != "0"  # A/B knob of grad_slot
@@ -635,9 +580,7 @@ def small_weight_bias_grad(dy2, x2, need_db, out_dtype, group=None):
     the reduction -- the caller's SlabGroup when given -- or None when the kernel does not cover the problem."""
     M, N = dy2.shape
     K = x2.shape[1]
-    if not (WGRAD_SMALL and dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and M < WGRAD_SMALL_MAX_ROWS
-            and N % 64 == 0 and K % 64 == 0 and dy2.stride(1) == 1 and x2.stride(1) == 1 and dy2.stride(0) % 8 == 0
-            and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):
+    if not (WGRAD_SMALL and _own_wgrad_operands(dy2, x2) and M < WGRAD_SMALL_MAX_ROWS and N % 64 == 0 and K % 64 == 0):
         return None
     lib = _lib.load()
     S = lib.grit_wgrad_small_splits(M, N, K)
@@ -700,15 +643,13 @@ def _rows_arg(row_scale, M):
 def long_weight_grad_partials(dy2, x2, need_db=False, row_scale=None):
     """fp32 partials [S, N, K] of dW = dy2^T x2 from the own kernel, or None where it does not apply (the library path runs).
     need_db: returns (partials, [S, N] fp32 column sums of dy2 per slice) -- the bias gradient as a by-product of the same launch."""
-    if not (WGRAD_TN and dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16):
-        return None
     M, N = dy2.shape
     K = x2.shape[1]
-    if M < 8192 or dy2.stride(1) != 1 or x2.stride(1) != 1:  # shorter maps: the deferred grouped kernel / the library
+    if not (WGRAD_TN and _own_wgrad_operands(dy2, x2) and M >= 8192):  # shorter maps: the deferred grouped kernel / the library
         return None
     lib = _lib.load()
     S = lib.grit_wgrad_tn_splits(M, N, K)
-    if S <= 0 or dy2.stride(0) % 8 or x2.stride(0) % 8 or dy2.data_ptr() % 16 or x2.data_ptr() % 16:
+    if S <= 0:
         return None
     part = torch.empty((S, N, K), dtype=torch.float32, device=dy2.device)
     bpart = torch.empty((S, N), dtype=torch.float32, device=dy2.device) if need_db else None
@@ -740,40 +681,28 @@ def long_weight_grad_with_parked(dy2, x2, group, weight, row_scale=None):
     None when nothing is parked or it does not apply (the parked jobs then stay for the scope's flush)."""
     parked = _deferral["parked"]
     if not (parked and WGRAD_PARK and WGRAD_TN_BIAS and getattr(weight, "_grit_wgrad_pickup", False) and group is not None
-            and dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and SlabGroup.ENABLED):
+            and SlabGroup.ENABLED and _own_wgrad_operands(dy2, x2)):
         return None
-    M, N = dy2.shape
-    K = x2.shape[1]
-    lib = _lib.load()
-    if (M < 8192 or dy2.stride(1) != 1 or x2.stride(1) != 1 or dy2.stride(0) % 8 or x2.stride(0) % 8 or dy2.data_ptr() % 16
-            or x2.data_ptr() % 16 or lib.grit_wgrad_tn_group_ok(M, N, K) != 1 or len(parked) + 1 > _lib.WGRAD_GROUP_MAX
-            or any(j[0].device != dy2.device for j in parked)):
+    mine = _job(dy2, x2, row_scale)
+    if (mine.M < 8192 or _lib.load().grit_wgrad_tn_group_ok(mine.M, mine.N, mine.K) != 1 or len(parked) + 1 > _lib.WGRAD_GROUP_MAX
+            or any(j.dy.device != dy2.device for j in parked)):
         return None
-    tiles = (N // 256) * (K // 256) + sum((j[7] // 256) * (j[8] // 256) for j in parked)
+    jobs = [mine] + parked
+    tiles = sum(j.tiles for j in jobs)
     if tiles > 256:
         return None
-    want = min([max(1, 256 // tiles), (M // 32) // 16 or 1] + [(j[6] // 32) // 16 or 1 for j in parked])
-    S = tn_slices(M, want)  # per problem: the slice count the kernel's contract admits for ITS row count
+    want = min([max(1, 256 // tiles)] + [j.max_slices for j in jobs])
+    splits = [tn_slices(j.M, want) for j in jobs]  # per problem: the slice count the kernel's contract admits for ITS row count
     _deferral["parked"] = []  # (from here on nothing may fail softly: the parked jobs are this launch's)
-    part = torch.empty((S, N, K), dtype=torch.float32, device=dy2.device)
-    bpart = torch.empty((S, N), dtype=torch.float32, device=dy2.device)
-    table = (_lib.WgradJob * (len(parked) + 1))()
-    table[0] = _lib.WgradJob(dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), M, N, K, S, part.data_ptr(), bpart.data_ptr(),
-                             *_rows_arg(row_scale, M))
-    flops = 2.0 * M * N * K
-    nbytes = 2.0 * M * (N + K) + 4.0 * S * N * K
-    for t, (pdy, px, pw_param, _, pw, _, pM, pN, pK, prs) in enumerate(parked):
-        pS = tn_slices(pM, want)
-        work = torch.empty(pS * pN * pK, dtype=torch.float32, device=dy2.device)
-        table[t + 1] = _lib.WgradJob(pdy.data_ptr(), pdy.stride(0), px.data_ptr(), px.stride(0), pM, pN, pK, pS, work.data_ptr(), None,
-                                     *_rows_arg(prs, pM))
-        group.add_raw(work, 1, 0, pS, pN * pK, pw, True)
-        _deferral["unverified"].append((pw_param, pw, "parked weight gradient [%d, %d]" % (pN, pK)))
-        flops += 2.0 * pM * pN * pK
-        nbytes += 2.0 * pM * (pN + pK) + 4.0 * pS * pN * pK
-    with _lib.device_guard(dy2.device), timed("gemm_own", flops=flops, kernel="wgrad_tn", bytes=nbytes):
-        st = lib.grit_wgrad_tn_grouped(table, len(parked) + 1, _lib.current_stream_ptr())
-    _lib.check(st, "grit_wgrad_tn_grouped")
+    part = torch.empty((splits[0], mine.N, mine.K), dtype=torch.float32, device=dy2.device)
+    bpart = torch.empty((splits[0], mine.N), dtype=torch.float32, device=dy2.device)
+    dw_partials = [part.data_ptr()]
+    for j, S in zip(parked, splits[1:]):
+        work = torch.empty(S * j.N * j.K, dtype=torch.float32, device=dy2.device)
+        dw_partials.append(work.data_ptr())
+        group.add_raw(work, 1, 0, S, j.N * j.K, j.w_out, True)
+        _deferral["unverified"].append((j.weight, j.w_check, "parked weight gradient [%d, %d]" % (j.N, j.K)))
+    _launch_grouped("tn", jobs, splits, dw_partials, [bpart.data_ptr()] + [None] * len(parked))
     return part, bpart
 
 
@@ -783,34 +712,19 @@ def long_weight_grads_together(pairs, row_scale=None):
     8 slices of 200 steps instead of 16 of 100: half the fp32 slices to write and to sum).  None when it does not apply."""
     if not (WGRAD_TN and WGRAD_TN_PAIR and len(pairs) > 1):
         return None
+    if not all(_own_wgrad_operands(dy2, x2) and dy2.shape[0] >= 8192 for dy2, x2 in pairs):
+        return None
+    jobs = [_job(dy2, x2, row_scale) for dy2, x2 in pairs]
     lib = _lib.load()
-    tiles = 0
-    for dy2, x2 in pairs:
-        M, N = dy2.shape
-        K = x2.shape[1]
-        if not (dy2.is_cuda and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and M >= 8192 and dy2.stride(1) == 1
-                and x2.stride(1) == 1 and dy2.stride(0) % 8 == 0 and x2.stride(0) % 8 == 0 and dy2.data_ptr() % 16 == 0
-                and x2.data_ptr() % 16 == 0 and lib.grit_wgrad_tn_group_ok(M, N, K) == 1):
-            return None
-        tiles += (N // 256) * (K // 256)
+    if not all(lib.grit_wgrad_tn_group_ok(j.M, j.N, j.K) == 1 for j in jobs):
+        return None
+    tiles = sum(j.tiles for j in jobs)
     if tiles > 256:
         return None
-    want = max(1, 256 // tiles)
-    want = min([want] + [(dy2.shape[0] // 32) // 16 or 1 for dy2, _ in pairs])
-    table = (_lib.WgradJob * len(pairs))()
-    parts = []
-    for t, (dy2, x2) in enumerate(pairs):
-        M, N = dy2.shape
-        K = x2.shape[1]
-        S = tn_slices(M, want)
-        part = torch.empty((S, N, K), dtype=torch.float32, device=dy2.device)
-        parts.append(part)
-        table[t] = _lib.WgradJob(dy2.data_ptr(), dy2.stride(0), x2.data_ptr(), x2.stride(0), M, N, K, S, part.data_ptr(), None,
-                                 *_rows_arg(row_scale, M))
-    with _lib.device_guard(pairs[0][0].device), timed("gemm_own", flops=2.0 * sum(d.shape[0] * d.shape[1] * x.shape[1] for d, x in pairs), kernel="wgrad_tn",
-                                                      bytes=sum(2.0 * d.shape[0] * (d.shape[1] + x.shape[1]) + 4.0 * p.numel() for (d, x), p in zip(pairs, parts))):
-        st = lib.grit_wgrad_tn_grouped(table, len(pairs), _lib.current_stream_ptr())
-    _lib.check(st, "grit_wgrad_tn_grouped")
+    want = min([max(1, 256 // tiles)] + [j.max_slices for j in jobs])
+    splits = [tn_slices(j.M, want) for j in jobs]
+    parts = [torch.empty((S, j.N, j.K), dtype=torch.float32, device=j.dy.device) for j, S in zip(jobs, splits)]
+    _launch_grouped("tn", jobs, splits, [p.data_ptr() for p in parts], [None] * len(jobs))
     return parts
 
 
@@ -860,8 +774,7 @@ def _own_linear(x, weight, bias):
     from grit_amd.ops import gemm as _gemm
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.numel() // x.shape[-1] >= min(512, _gemm.SHORT_MIN_ROWS)):
         return None
-    x2 = x.reshape(-1, x.shape[-1])
-    y = _gemm.long_linear(x2 if x2.is_contiguous() else x2.contiguous(), weight, bias)
+    y = _gemm.long_linear(_rows(x), weight, bias)
     return None if y is None else y.view(x.shape[:-1] + (weight.shape[0],))
 
 
@@ -877,6 +790,16 @@ def _own_input_grad(dy2, weight, shape):
     from grit_amd.ops import gemm as _gemm
     dx = _gemm.long_input_grad(dy2, weight)
     return None if dx is None else dx.view(shape)
+
+
+def projection_input_grad(dy2, weight_obj, weight, shape):
+    """dX = dy2 @ W of a plain projection, viewed as `shape`: the own kernel where its policy takes the problem (weight_obj: the tensor
+    object the forward was called with -- transposed copies are attached to it), else the library GEMM."""
+    dx = _own_input_grad(dy2, weight_obj, shape)
+    if dx is None:
+        with timed("gemm_lib", **gemm_work(dy2.shape[0], weight.shape[1], weight.shape[0])):
+            dx = torch.mm(dy2, weight).view(shape)
+    return dx
 
 
 def leave_bias_extra(bias, term):
@@ -905,8 +828,7 @@ class _LinearFn(Function):
             # holder (grit_amd/ops/layer_norm.py), else here, from the saved output
             from grit_amd.ops import gemm as _gemm
             p, seed_dev, holder = relu
-            x2 = x.reshape(-1, x.shape[-1])
-            y = _gemm.gemm_nt_relu(x2 if x2.is_contiguous() else x2.contiguous(), weight, _gemm.BIAS_RELU_DROP, bias=bias, p=p,
+            y = _gemm.gemm_nt_relu(_rows(x), weight, _gemm.BIAS_RELU_DROP, bias=bias, p=p,
                                    seed_dev=seed_dev).view(x.shape[:-1] + (weight.shape[0],))
             ctx.relu = (p, holder, seed_dev is not None)
             ctx.save_for_backward(*((x, weight, y) + ((seed_dev,) if seed_dev is not None else ())))
@@ -917,7 +839,6 @@ class _LinearFn(Function):
         # of a sample with factor 0 come back as exact zeros in dy (wgrad_tn.hip then skips them in the weight gradient)
         ctx.row_scale = row_scale
         ctx.bias_param = bias if single_use else None  # the parameter itself: the deferred path checks its .grad
-        ctx.weight_param = weight if single_use else None
         ctx.weight_obj = weight  # the tensor object the forward was called with: transposed copies are attached to IT
         ctx.bias_obj = bias      # ... and a gradient term another node leaves for this bias (take_bias_extra)
         if relu is not None:
@@ -936,12 +857,7 @@ class _LinearFn(Function):
         if ctx.relu is not None and not ctx.relu[1].get("fused"):
             from grit_amd.ops.glue import relu_dropout_backward
             dy = relu_dropout_backward(saved[2], dy, ctx.relu[0], saved[3] if ctx.relu[2] else None)  # (no consumer took it over)
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        dy2, x2 = _rows(dy), _rows(x)
         dx = dw = db = None
         if ctx.row_scale is not None:
             backend.check_dropped_rows(dy2, ctx.row_scale[0], "Linear backward (row_scale)")
@@ -953,32 +869,18 @@ class _LinearFn(Function):
             defer_weight_bias_grad(dy2, x2, weight, ctx.bias_param, ctx.needs_input_grad[1], need_b, ctx.single_use)
         if deferred is not None:  # short map inside a gradient-bucket scope: dW / db come from the scope's grouped launch
             dw, db = deferred
-            if ctx.needs_input_grad[0]:
-                dx = _own_input_grad(dy2, ctx.weight_obj, x.shape)
-                if dx is None:
-                    with timed("gemm_lib", **gemm_work(dy2.shape[0], weight.shape[1], weight.shape[0])):
-                        dx = torch.mm(dy2, weight).view(x.shape)
-            return dx, dw, db, None, None, None
-        side = fork(dy2, x2, rows=dy2.shape[0], single_use=ctx.single_use) \
-            if (ctx.needs_input_grad[0] and (ctx.needs_input_grad[1] or need_b)) else None
-        group = SlabGroup() if dy2.is_cuda else None  # dW's and db's partial sums: one reduction launch
-        with on_stream(side):
+        else:
+            group = SlabGroup() if dy2.is_cuda else None  # dW's and db's partial sums: one reduction launch
             both = small_weight_bias_grad(dy2, x2, need_b, weight.dtype, group) if (ctx.needs_input_grad[1] and extra is None) else None
             if both is not None:  # short map: dW and db partials from one launch
                 dw, db = both
             else:
                 dw, db = weight_bias_grad(dy2, x2, group, ctx.needs_input_grad[1], need_b, weight, row_scale=ctx.row_scale,
                                           bias_extra=extra)
-            if side is None:
-                finish_group(group, ctx.single_use, [(ctx.weight_param, dw), (ctx.bias_param, db)])
-            elif group is not None:
+            if group is not None:
                 group.run()
         if ctx.needs_input_grad[0]:
-            dx = _own_input_grad(dy2, ctx.weight_obj, x.shape)
-            if dx is None:
-                with timed("gemm_lib", **gemm_work(dy2.shape[0], weight.shape[1], weight.shape[0])):
-                    dx = torch.mm(dy2, weight).view(x.shape)
-        join(side, dw, db)
+            dx = projection_input_grad(dy2, ctx.weight_obj, weight, x.shape)
         return dx, dw, db, None, None, None
 
 
@@ -1029,15 +931,13 @@ class _SharedInputLinearsFn(Function):
     def backward(ctx, *dys):
         x, weights = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         n = ctx.n
-        x2 = x.reshape(-1, x.shape[-1])
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        x2 = _rows(x)
         dx2, dws, dbs = None, [None] * n, [None] * n
         group = SlabGroup() if x2.is_cuda else None
         for l in range(n):
             if dys[l] is None:
                 continue
-            dy2 = dys[l].reshape(-1, dys[l].shape[-1])
-            dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
+            dy2 = _rows(dys[l])
             if ctx.needs_input_grad[0]:
                 with timed("gemm_lib", **gemm_work(dy2.shape[0], weights[l].shape[1], weights[l].shape[0])):
                     if dx2 is None:
@@ -1066,7 +966,8 @@ def shared_input_linears(x, linears):
 
 def linear(x, weight, bias, single_use=False, row_scale=None):
     """F.linear with the backward of this module.  single_use=True: the caller guarantees `weight` / `bias` receive exactly one
-    gradient per backward pass (not shared between call sites), which lets small maps compute them beside the chain (fork).
+    gradient per backward pass (not shared between call sites), which lets their gradients wait for the gradient bucket's grouped launch
+    (defer_weight_bias_grad).
     row_scale = (factors [B] float32 on the device, rows per sample) or None: drop-path factors of the branch the result feeds; the caller
     guarantees that the gradient of the result is exactly zero in the rows of samples whose factor is 0 (the weight gradient skips them)."""
     fits = (backend.override() is None and x.is_cuda and torch.is_grad_enabled()

@@ -21,8 +21,8 @@ from grit_amd.ops import backend
 from grit_amd.ops import gemm as G
 from grit_amd.ops import layer_norm as LN
 from grit_amd.ops import transposed as _transposed
-from grit_amd.ops.linear import (WGRAD_STREAM, SlabGroup, column_sum, defer_weight_bias_grad, finish_group, fork, grad_slot, join,
-                                 long_weight_grads_together, on_stream, single_use_now, slab_sum, weight_grad)
+from grit_amd.ops.linear import (SlabGroup, _rows, column_sum, defer_weight_bias_grad, grad_slot, long_weight_grads_together,
+                                 single_use_now, slab_sum, weight_grad)
 from grit_amd.ops.profiling import gemm_work, timed
 
 MIN_ROWS = 2048
@@ -32,70 +32,53 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
-def _rows(t):
-    t2 = t.reshape(-1, t.shape[-1])
-    return t2 if t2.is_contiguous() else t2.contiguous()
-
-
 def _mlp_backward(d_branch, n2, w1, pre, act, w2, needs, need_b2=False, group=None, params=None, row_scale=None, rows_per_sample=0):
-    """Gradients of branch = fc2(gelu(fc1(n2))) w.r.t. (n2, w1, b1, w2[, b2]) given d_branch [M, C].  The chain of input
-    gradients runs on the current stream, the weight / bias gradients beside it on the side stream (linear.fork).  `group`:
-    the caller's SlabGroup -- every partial sum of the node (dW2, db1, dW1[, db2]) is then reduced by the caller's one launch
-    (not combined with the side stream: the knob that enables it is an A/B diagnostic)."""
+    """Gradients of branch = fc2(gelu(fc1(n2))) w.r.t. (n2, w1, b1, w2[, b2]) given d_branch [M, C].  `group`: the caller's
+    SlabGroup -- every partial sum of the node (dW2, db1, dW1[, db2]) is then reduced by the caller's one launch."""
     need_x, need_w1, need_b1, need_w2 = needs
     if row_scale is not None and rows_per_sample > 0:
         backend.check_dropped_rows(d_branch, row_scale, "Mlp backward (drop-path factors)")
     d_n2 = d_w1 = d_b1 = d_w2 = d_b2 = None
     chain = need_x or need_w1 or need_b1
-    side = fork(d_branch, act) if (chain and (need_w2 or need_b2)) else None
-    if side is not None:
-        group = None
     # params = (fc1.weight, fc2.weight) as Parameters when the module is declared single-use: inside a gradient-bucket scope the two
     # weight gradients then join the scope's grouped launch (ops.linear.defer_weight_bias_grad) instead of running here
     rs = (row_scale, rows_per_sample) if (row_scale is not None and rows_per_sample > 0) else None  # (the weight gradients skip dropped samples)
-    dfr2 = defer_weight_bias_grad(d_branch, act, params[1], None, need_w2, False, True, row_scale=rs) if (params is not None and side is None) else None
+    dfr2 = defer_weight_bias_grad(d_branch, act, params[1], None, need_w2, False, True, row_scale=rs) if params is not None else None
     # both weight gradients of the node in one grouped launch (after d_pre exists): see linear.long_weight_grads_together
-    together = dfr2 is None and side is None and group is not None and need_w2 and need_w1 and chain
-    with on_stream(side):
-        if dfr2 is not None:
-            d_w2 = dfr2[0]
-        elif need_w2 and not together:
-            d_w2 = weight_grad(d_branch, act, group, param=w2, row_scale=rs)
-        if need_b2:
-            d_b2 = column_sum(d_branch, w2.dtype, group)
+    together = dfr2 is None and group is not None and need_w2 and need_w1 and chain
+    if dfr2 is not None:
+        d_w2 = dfr2[0]
+    elif need_w2 and not together:
+        d_w2 = weight_grad(d_branch, act, group, param=w2, row_scale=rs)
+    if need_b2:
+        d_b2 = column_sum(d_branch, w2.dtype, group)
     if chain:
         w2t = _transposed.lookup(params[1] if params is not None else w2)  # made for all blocks at once by the backbone's forward
         # (row_scale: the drop-path factors already applied to the rows of d_branch -- tiles of dropped samples are zeros without a K loop)
         d_pre, partial = G.input_grad_dgelu(d_branch, w2t if w2t is not None else w2.t().contiguous(), pre, row_scale, rows_per_sample)
-        join(side, d_w2, d_b2)
-        side = fork(d_pre, partial, n2) if (need_x and (need_w1 or need_b1)) else None
-        if side is not None:
-            group = None
-        with on_stream(side):
-            if need_b1:
-                d_b1 = (group.add(partial.unsqueeze(0), w1.dtype) if group is not None else slab_sum(partial.unsqueeze(0), w1.dtype))[0]
-            dfr1 = defer_weight_bias_grad(d_pre, n2, params[0], None, need_w1, False, True, row_scale=rs) if (params is not None and side is None) else None
-            parts = long_weight_grads_together([(d_branch, act), (d_pre, n2)], row_scale=rs) if (together and dfr1 is None) else None
-            if parts is not None:
-                outs = []
-                for part, (wt, dyt, xt) in zip(parts, ((w2, d_branch, act), (w1, d_pre, n2))):
-                    slot = grad_slot(wt, dyt.dtype, dyt.device)
-                    outs.append(group.add(part.unsqueeze(0), dyt.dtype,
-                                          out=None if slot is None else slot.view(1, dyt.shape[1], xt.shape[1]))[0])
-                d_w2, d_w1 = outs
-            else:
-                if together:
-                    d_w2 = weight_grad(d_branch, act, group, param=w2, row_scale=rs)
-                if dfr1 is not None:
-                    d_w1 = dfr1[0]
-                elif need_w1:
-                    d_w1 = weight_grad(d_pre, n2, group, param=w1, row_scale=rs)
+        if need_b1:
+            d_b1 = (group.add(partial.unsqueeze(0), w1.dtype) if group is not None else slab_sum(partial.unsqueeze(0), w1.dtype))[0]
+        dfr1 = defer_weight_bias_grad(d_pre, n2, params[0], None, need_w1, False, True, row_scale=rs) if params is not None else None
+        parts = long_weight_grads_together([(d_branch, act), (d_pre, n2)], row_scale=rs) if (together and dfr1 is None) else None
+        if parts is not None:
+            outs = []
+            for part, (wt, dyt, xt) in zip(parts, ((w2, d_branch, act), (w1, d_pre, n2))):
+                slot = grad_slot(wt, dyt.dtype, dyt.device)
+                outs.append(group.add(part.unsqueeze(0), dyt.dtype,
+                                      out=None if slot is None else slot.view(1, dyt.shape[1], xt.shape[1]))[0])
+            d_w2, d_w1 = outs
+        else:
+            if together:
+                d_w2 = weight_grad(d_branch, act, group, param=w2, row_scale=rs)
+            if dfr1 is not None:
+                d_w1 = dfr1[0]
+            elif need_w1:
+                d_w1 = weight_grad(d_pre, n2, group, param=w1, row_scale=rs)
         if need_x:
             d_n2 = G.long_input_grad(d_pre, params[0] if params is not None else w1)  # NT on fc1.weight^T (own kernel / library NT)
             if d_n2 is None:
                 with timed("gemm_lib", **gemm_work(d_pre.shape[0], w1.shape[1], w1.shape[0])):
                     d_n2 = torch.mm(d_pre, w1)
-        join(side, d_b1, d_w1)
     return d_n2, d_w1, d_b1, d_w2, d_b2
 
 
@@ -104,7 +87,7 @@ class _MlpFn(Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, single_use=False):
-        ctx.params = (w1, b1, w2, b2) if single_use else None
+        ctx.params = (w1, w2) if single_use else None  # the Parameters themselves: the deferred path checks their .grad
         x2 = _rows(x)
         pre, act = G.linear_bias_gelu(x2, w1, b1)
         out = G.long_linear(act, w2, b2)  # (the stage-0 map: the own narrow-output kernel; None elsewhere)
@@ -122,11 +105,9 @@ class _MlpFn(Function):
         d_branch = _rows(dy)
         ni = ctx.needs_input_grad
         group = SlabGroup()
-        ps = ctx.params
         d_x, d_w1, d_b1, d_w2, d_b2 = _mlp_backward(d_branch, x2, w1, pre, act, w2, (ni[0], ni[1], ni[2], ni[3]), ni[4], group,
-                                                    params=None if ps is None else (ps[0], ps[2]))
-        finish_group(group, ps is not None and not WGRAD_STREAM, [] if ps is None else
-                     [(ps[0], d_w1), (ps[1], d_b1), (ps[2], d_w2), (ps[3], d_b2)])
+                                                    params=ctx.params)
+        group.run()
         return (None if d_x is None else d_x.view(ctx.shape)), d_w1, d_b1, d_w2, d_b2, None
 
 
@@ -135,7 +116,7 @@ class _MlpAddLayerNormFn(Function):
 
     @staticmethod
     def forward(ctx, x_in, w1, b1, w2, b2, shortcut, scale, weight, bias, eps, single_use=False):
-        ctx.params = (w1, b1, w2, b2, weight, bias) if single_use else None
+        ctx.params = (w1, w2) if single_use else None  # see _MlpFn
         x2 = _rows(x_in)
         # (scale: the drop-path factors of this branch -- the fc1 tiles of samples it removes are not computed)
         pre, act = G.linear_bias_gelu(x2, w1, b1, scale, x2.shape[0] // shortcut.shape[0] if scale is not None else 0)
@@ -176,14 +157,10 @@ class _MlpAddLayerNormFn(Function):
         group = SlabGroup()  # LayerNorm sums, dW2, db1, dW1: one reduction launch for the whole node
         dx, d_branch, sums = LN._add_layer_norm_backward(x, weight, mean, rstd, scale, gx, gy, ctx.shape[0], True, 0.0, None, group)
         ni = ctx.needs_input_grad
-        ps = ctx.params
         d_x, d_w1, d_b1, d_w2, _ = _mlp_backward(d_branch, x2, w1, pre, act, w2, (ni[0], ni[1], ni[2], ni[3]), group=group,
-                                                 params=None if ps is None else (ps[0], ps[2]), row_scale=scale,
+                                                 params=ctx.params, row_scale=scale,
                                                  rows_per_sample=x2.shape[0] // ctx.shape[0] if scale is not None else 0)
-        # (sums in another dtype than the parameters would be converted -- read -- below, before a deferred launch has run)
-        finish_group(group, ps is not None and not WGRAD_STREAM and sums.dtype == w2.dtype and ni[4] and ni[7] and ni[8],
-                     [] if ps is None else [(ps[0], d_w1), (ps[1], d_b1), (ps[2], d_w2), (ps[3], sums[2]), (ps[4], sums[0]),
-                                            (ps[5], sums[1])])
+        group.run()  # (before the return below converts -- reads -- the sums)
         return ((None if d_x is None else d_x.view(ctx.in_shape)), d_w1, d_b1, d_w2, sums[2].to(w2.dtype), dx.view(ctx.shape),
                 None, sums[0], sums[1], None, None)
 

@@ -93,8 +93,7 @@ def test_slot_is_handed_out_once_and_only_for_open_buckets():
         ddp._pack(ddp._where[net.w2])
         assert L.grad_slot(net.w2, torch.float32, torch.device('cpu')) is None  # bucket already packed
     finally:
-        L.abandon_deferred()
-        L._deferral["active"] = False
+        L.abandon_scope()
     del out
     # a parameter used twice in one pass: the engine must see TWO distinct gradient tensors (sum 3 dW, not 2 x the last one)
     net2 = _Net()

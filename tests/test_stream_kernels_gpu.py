@@ -355,59 +355,6 @@ def test_shared_input_linears_match_separate_linears(dtype):
             torch.testing.assert_close(g.float(), w.float(), **tol)
 
 
-def test_small_map_weight_gradients_beside_the_chain_equal_the_inline_ones(monkeypatch):
-    """GRIT_WGRAD_STREAM_SMALL: inside a gradient-bucket wrapper's scope the weight / bias gradients of single-use Linears on
-    small maps run on a side stream and the main stream waits only when the wrapper packs them.  Same numbers as with the
-    knob off, bit for bit; a Linear applied twice (not declared single-use) is untouched by the mechanism; after
-    finish_gradient_sync nothing is pending."""
-    from grit_amd.ddp import BucketedDataParallel
-    from grit_amd.ops import linear as L
-    from grit_amd.ops.layer_norm import linear_add_layer_norm
-
-    class Net(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.a = torch.nn.ModuleList(L.Linear(512, 1024) for _ in range(3))
-            self.b = torch.nn.ModuleList(torch.nn.Linear(1024, 512) for _ in range(3))
-            self.norm = torch.nn.LayerNorm(512)
-            self.twice = L.Linear(512, 512)
-            L.mark_single_use(self.a, self.b)
-
-        def forward(self, x):
-            for a, b in zip(self.a, self.b):
-                h = torch.relu(a(x))
-                x = linear_add_layer_norm(h, b, x, None, self.norm.weight, self.norm.bias, 1e-5, 0.0, True)[1]
-                x = self.twice(self.twice(x))
-            return x
-
-    torch.manual_seed(0)
-    net = Net().to(DEV).bfloat16()
-    x = torch.randn(8, 600, 512, device=DEV).bfloat16()
-    cot = torch.randn(8, 600, 512, device=DEV).bfloat16()
-    ddp = BucketedDataParallel(net, bucket_mb=1)
-    monkeypatch.setattr(L, "WGRAD_DEFER", False)  # this test is about the side-stream variant of the per-node path
-    results = []
-    for knob in (False, True, True):
-        monkeypatch.setattr(L, "WGRAD_STREAM_SMALL", knob)
-        forks = []
-        real_fork = L.fork
-        monkeypatch.setattr(L, "fork", lambda *a, **k: (forks.append(real_fork(*a, **k)) or forks[-1]))
-        import grit_amd.ops.layer_norm as LNmod
-        monkeypatch.setattr(LNmod, "fork", L.fork)
-        (ddp(x).float() * cot.float()).sum().backward()
-        deferred = sum(1 for f in forks if f is not None and getattr(f, "deferred", False))
-        ddp.finish_gradient_sync()
-        assert not L._deferral["pending"] and not L._deferral["active"]
-        torch.cuda.synchronize()
-        results.append(({n: p.grad.clone() for n, p in net.named_parameters()}, deferred))
-        monkeypatch.setattr(L, "fork", real_fork)
-        monkeypatch.setattr(LNmod, "fork", real_fork)
-    # b[0..2], a[1..2] (a[0] reads the input, which needs no gradient: nothing to overlap with); `twice` never
-    assert results[0][1] == 0 and results[1][1] == 5 and results[2][1] == 5
-    for n, g in results[0][0].items():
-        assert torch.equal(g, results[1][0][n]) and torch.equal(g, results[2][0][n]), n
-
-
 def test_deferred_grouped_weight_gradients(monkeypatch):
     """GRIT_WGRAD_DEFER: inside a gradient-bucket wrapper's scope the single-use Linears of short maps return EMPTY weight / bias
     gradients that the wrapper fills with one grouped launch before it packs them (grit_wgrad_small_grouped + one grouped slab
