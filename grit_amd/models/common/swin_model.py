@@ -33,7 +33,9 @@ from grit_amd.ops import backend as _backend
 from grit_amd.ops.layer_norm import LayerNorm, add_layer_norm, linear_add_layer_norm, merge_layer_norm
 from grit_amd.ops import transposed as _transposed
 from grit_amd.ops.linear import Linear, linear, mark_single_use, park_weight_grad_for_partner
-from grit_amd.ops.mlp import hidden as fused_hidden, mlp as fused_mlp, mlp_add_layer_norm
+from grit_amd.ops import layer_norm as _layer_norm
+from grit_amd.ops import mlp as _mlp_ops
+from grit_amd.ops.mlp import hidden as fused_hidden, mlp as fused_mlp, mlp_add_layer_norm, mlp_norm_residual
 from grit_amd.ops.rel_bias import relative_position_bias, relative_position_bias_grouped
 from grit_amd.ops.window_attention import window_attention
 
@@ -231,7 +233,24 @@ class SwinTransformerBlock(nn.Module):
             # yields the projection's bias gradient): attn.proj -> norm2, mlp.fc2 -> the next block's norm1
             scale_a = self._drop_path_scale(x, torch.float32)  # (drawn BEFORE the attention runs: its qkv Linear is told about it)
             heads = self.attn.attend_heads(n1, H, W, self.shift_size, row_scale=None if scale_a is None else (scale_a, L))
-            x, n2 = self._residual_linear_norm(x, heads, self.attn.proj, self.norm2, scale=scale_a, drawn=True)
+            # Without autograd at C = 128 (the frozen stage 0, inference) the whole Mlp half is one launch (grit_mlp_s0_fwd_bf16, same
+            # values): norm2(x) is never materialised -- the projection's residual epilogue produces x alone
+            one_launch = (_FUSED_MLP and _mlp_ops.S0_MLP_FUSED and scale_a is None and not self._drop_path_active()
+                          and _mlp_ops.mlp_norm_residual_applies(x, self.norm2, self.mlp, next_norm))
+            n2 = xr = None
+            if one_launch and self.attn.proj.bias is not None and not (
+                    torch.is_grad_enabled() and (heads.requires_grad or self.attn.proj.weight.requires_grad or self.attn.proj.bias.requires_grad)):
+                xr = _layer_norm._residual_linear(heads, self.attn.proj.weight, self.attn.proj.bias, x.view(-1, C), None, L)
+            if xr is not None:
+                x = xr.view(x.shape)
+            else:
+                x, n2 = self._residual_linear_norm(x, heads, self.attn.proj, self.norm2, scale=scale_a, drawn=True)
+            if one_launch:
+                fused = mlp_norm_residual(x, self.norm2, self.mlp, next_norm)
+                if fused is not None:
+                    return fused
+                if n2 is None:
+                    n2 = self.norm2(x)
             if next_norm is None:
                 return self._residual(x, self.mlp.run(n2))
             # fc1 + GELU + fc2 + drop-path + residual + the next block's norm1 as one node (fused-epilogue GEMMs)
@@ -259,6 +278,11 @@ class SwinTransformerBlock(nn.Module):
             keep = 1.0 - dp.drop_prob
             return torch.empty(x.shape[0], dtype=dtype, device=x.device).bernoulli_(keep).div_(keep)
         return None
+
+    def _drop_path_active(self):
+        """Whether _drop_path_scale draws factors in this call (asked without drawing any)."""
+        dp = self.drop_path
+        return isinstance(dp, DropPath) and dp.drop_prob > 0. and self.training
 
     def _residual(self, x, branch):
         """x + drop_path(branch) as ONE elementwise kernel (addcmul with the per-sample keep/scale mask)."""

@@ -8,8 +8,13 @@ follows it (drop-path, residual add, the next LayerNorm; :289-298) as ONE autogr
             fc2 input gradient x GELU'   grit_gemm_bf16_nt / GRIT_GEMM_DGELU       (also fc1's bias gradient, as slab sums)
             weight gradients, fc1 input gradient: library GEMMs (split-M, grit_amd/ops/linear.py)
 
-Nothing else touches the [M, 4C] hidden map: no GELU, GeluBackward or column-sum kernel (4.8 + 2 ms of the 67 ms step)."""
+Nothing else touches the [M, 4C] hidden map: no GELU, GeluBackward or column-sum kernel (4.8 + 2 ms of the 67 ms step).
+
+Without autograd at C = 128 (the frozen stage 0 of a training step, inference) the whole Mlp half of a block -- norm2, fc1 + GELU,
+fc2, the residual add and the next block's norm1 -- is ONE launch, grit_mlp_s0_fwd_bf16 (mlp_norm_residual): the hidden map never
+exists."""
 import ctypes
+import os
 
 import torch
 import torch.nn.functional as F
@@ -26,6 +31,10 @@ from grit_amd.ops.linear import (SlabGroup, _rows, column_sum, defer_weight_bias
 from grit_amd.ops.profiling import gemm_work, timed
 
 MIN_ROWS = 2048
+# GRIT_S0_MLP_FUSED (default 1): without autograd (the frozen stage 0 of a training step, inference) the Mlp half of a C = 128 block --
+# norm2, fc1 + GELU, fc2, the residual add and the next block's norm1 -- is one launch (grit_mlp_s0_fwd_bf16) with the same values.
+# 0: the separate launches.
+S0_MLP_FUSED = os.environ.get("GRIT_S0_MLP_FUSED", "1") != "0"
 
 
 def _ptr(t):
@@ -218,3 +227,53 @@ def mlp_add_layer_norm(x_in, module, shortcut, scale, norm):
     return _MlpAddLayerNormFn.apply(x_in, fc1.weight, fc1.bias, fc2.weight, fc2.bias, shortcut, scale, norm.weight.contiguous(),
                                     norm.bias.contiguous(), float(norm.eps),
                                     single_use_now(getattr(fc1, "single_use", False) and getattr(fc2, "single_use", False)))
+
+
+def _plain_norm(norm, C):
+    return (isinstance(norm, LN.LayerNorm) and norm.elementwise_affine and tuple(norm.normalized_shape) == (C,)
+            and norm.weight.dtype == norm.bias.dtype == torch.bfloat16 and norm.weight.is_contiguous() and norm.bias.is_contiguous())
+
+
+def mlp_norm_residual_applies(x, norm, module, next_norm=None):
+    """Whether mlp_norm_residual(x, norm, module, next_norm) runs the one-launch kernel: no autograd for any tensor involved, a bf16
+    Mlp the fused GEMM path takes (_fits) with C = 128 and 512 hidden channels, plain affine bf16 LayerNorms over the last dimension,
+    contiguous rows."""
+    C = x.shape[-1]
+    if not (C == 128 and _fits(x, module) and x.is_contiguous() and x.data_ptr() % 16 == 0):
+        return False
+    fc1, fc2 = module.fc1, module.fc2
+    if tuple(fc1.weight.shape) != (512, 128) or tuple(fc2.weight.shape) != (128, 512) or fc2.bias.dtype != torch.bfloat16:
+        return False
+    norms = (norm,) if next_norm is None else (norm, next_norm)
+    if not all(_plain_norm(n, C) for n in norms):
+        return False
+    if torch.is_grad_enabled():
+        tensors = [x, fc1.weight, fc1.bias, fc2.weight, fc2.bias] + [t for n in norms for t in (n.weight, n.bias)]
+        if any(t.requires_grad for t in tensors):
+            return False
+    return True
+
+
+def mlp_norm_residual(x, norm, module, next_norm=None):
+    """x_out = x + module(norm(x)) for the Mlp of a Swin block whose drop path is inactive in this call -- or (x_out, next_norm(x_out))
+    with `next_norm` -- as ONE launch (grit_mlp_s0_fwd_bf16: norm(x) and the hidden map never reach memory; bit for bit the values of the
+    separate launches).  None where the kernel does not apply (mlp_norm_residual_applies)."""
+    if not mlp_norm_residual_applies(x, norm, module, next_norm):
+        return None
+    fc1, fc2 = module.fc1, module.fc2
+    x2 = _rows(x)
+    x_out = torch.empty_like(x2)
+    n_out = torch.empty_like(x2) if next_norm is not None else None
+    rows = x2.shape[0]
+    work = {"rows": rows, "flops": 4.0 * rows * 512 * 128, "bytes": 2.0 * (rows * 128 * (2 if n_out is None else 3) + 2 * 512 * 128)}
+    with _lib.device_guard(x.device), timed("gemm_own", kernel="mlp_s0_fwd", **work):
+        st = _lib.load().grit_mlp_s0_fwd_bf16(_ptr(x2), _ptr(norm.weight), _ptr(norm.bias), float(norm.eps), _ptr(fc1.weight),
+                                              _ptr(fc1.bias), _ptr(fc2.weight), _ptr(fc2.bias),
+                                              _ptr(next_norm.weight if next_norm is not None else None),
+                                              _ptr(next_norm.bias if next_norm is not None else None),
+                                              float(next_norm.eps) if next_norm is not None else 0.0, x2.shape[0], 128, 512,
+                                              _ptr(x_out), _ptr(n_out), _lib.current_stream_ptr())
+    _lib.check(st, "grit_mlp_s0_fwd_bf16")
+    if next_norm is None:
+        return x_out.view(x.shape)
+    return x_out.view(x.shape), n_out.view(x.shape)

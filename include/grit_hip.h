@@ -63,7 +63,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 49
+#define GRIT_ABI_VERSION 50
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -651,6 +651,16 @@ int grit_gemm_bf16_nt_relu(const void* A, long lda, const void* B, long ldb, voi
 int grit_gemm_bf16_nt_rows(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K, int epilogue,
                            const void* bias, void* aux, long ldaux, float* colsum, const float* row_scale, int rows_per_sample,
                            int variant, void* stream);
+/* The Mlp half of a frozen stage-0 Swin block in one launch (grit_amd/csrc/mlp_s0.hip; forward only, no dropout, no drop path):
+ *     x_out = x + fc2(gelu(fc1(LayerNorm(x; norm_w, norm_b, eps)) + b1)) + b2        n_out = LayerNorm(x_out; next_w, next_b, next_eps)
+ * x, x_out, n_out [rows, C] bf16 contiguous; w1 [hidden, C], w2 [C, hidden], biases and norm parameters bf16.  next_w / next_b / n_out all
+ * NULL: no second LayerNorm.  Bit for bit the values of grit_layernorm_fwd -> grit_gemm_bf16_nt / GRIT_GEMM_BIAS_GELU (aux NULL) ->
+ * grit_gemm_bf16_nt_res without factors (= GRIT_GEMM_BIAS + a bf16 add) -> grit_layernorm_fwd; the hidden map and the first LayerNorm's
+ * output never reach memory.  C == 128 and hidden == 512 only (GRIT_ERR_UNSUPPORTED otherwise); any rows >= 1, rows past the end are
+ * neither read nor written; x_out and n_out must not alias x; pointers 16-byte aligned (b1, b2: 8). */
+int grit_mlp_s0_fwd_bf16(const void* x, const void* norm_w, const void* norm_b, float eps, const void* w1, const void* b1,
+                         const void* w2, const void* b2, const void* next_w, const void* next_b, float next_eps, int rows, int C,
+                         int hidden, void* x_out, void* n_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Beam-search candidate selection (reference models/caption/transformer.py:184-188: descending sort of the flattened
