@@ -46,6 +46,9 @@ class FlatAdam(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
                         capturable=False, differentiable=False, fused=None)
         super().__init__(params, defaults)
+        self._attach(owner)
+
+    def _attach(self, owner):
         self._owner = owner
         mine = {p for g in self.param_groups for p in g['params']}
         self._mine = mine
@@ -60,7 +63,7 @@ class FlatAdam(torch.optim.Optimizer):
     def _derive_runs(self):
         """(run, parameters, steps taken) for every contiguous range of live parameters of one age, clipped to this rank's
         slice when the optimizer is sharded."""
-        self._runs = self._owner._runs(self._mine, key=self._steps.get)
+        self._runs = self._keyed_runs()
         self._layout_version = self._owner.ddp.layout_version
         # A step captured in a HIP graph holds, per run, the run's (start, n) and the ADDRESS of its row of the device table of
         # per-step scalars: a captured step is valid for exactly one value of `runs_version` (grit_amd/engine/graph_step.py checks it),
@@ -72,6 +75,9 @@ class FlatAdam(torch.optim.Optimizer):
         ages = {self._steps[p] for _, params, _ in self._runs for p in params}
         self._split_ages = any(id(p) not in stepped and self._steps[p] in ages for p in self._mine)
         self._link_state()
+
+    def _keyed_runs(self):
+        return self._owner._runs(self._mine, key=self._steps.get)
 
     def _link_state(self):
         for g in self.param_groups:
@@ -115,7 +121,6 @@ class FlatAdam(torch.optim.Optimizer):
         """Write {lr / bias_correction1, 1 / sqrt(bias_correction2)} of the step every run is ABOUT to take into the device table
         the launches read (pinned host copy -> one asynchronous H2D copy on the current stream).  grit_amd.engine.graph_step calls
         this before every replay of a captured step; step() calls it itself when it is not being captured."""
-        lr, b1, b2, _ = self._hyper()
         n = max(self._HYPER_ROWS, len(self._runs))
         dev = self._runs[0][0][2].device if self._runs else torch.device('cpu')
         if getattr(self, '_hyper_host', None) is None or self._hyper_host.shape[1] < len(self._runs) or \
@@ -123,9 +128,9 @@ class FlatAdam(torch.optim.Optimizer):
             # The staging copy is a RING of pinned tables: an asynchronous H2D copy reads the pinned memory when it EXECUTES, and a
             # host that runs ahead of the device (no host sync per step) would otherwise overwrite step k's scalars with step k+1's
             # before step k's copy has run.  A slot is rewritten only after the copy that read it last has completed (its event).
-            shape = (self._HYPER_SLOTS, n, 2)
+            shape = (self._HYPER_SLOTS, n, self._HYPER_COLS)
             self._hyper_host = torch.zeros(shape, dtype=torch.float32).pin_memory() if dev.type == 'cuda' else torch.zeros(shape)
-            self._hyper_dev = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+            self._hyper_dev = torch.zeros((n, self._HYPER_COLS), dtype=torch.float32, device=dev)
             self._hyper_events = [None] * self._HYPER_SLOTS
             self._hyper_slot = 0
         slot = self._hyper_slot
@@ -133,17 +138,22 @@ class FlatAdam(torch.optim.Optimizer):
         if self._hyper_events[slot] is not None:
             self._hyper_events[slot].synchronize()
         host = self._hyper_host[slot]
-        for i, (_, _, age) in enumerate(self._runs):
-            t = age + 1
-            host[i, 0] = lr / (1.0 - b1 ** t)
-            host[i, 1] = 1.0 / math.sqrt(1.0 - b2 ** t)
+        self._fill_hyper(host)
         self._hyper_dev.copy_(host, non_blocking=True)
         if self._hyper_dev.is_cuda:
             if self._hyper_events[slot] is None:
                 self._hyper_events[slot] = torch.cuda.Event()
             self._hyper_events[slot].record()
 
+    def _fill_hyper(self, host):
+        lr, b1, b2, _ = self._hyper()
+        for i, (_, _, age) in enumerate(self._runs):
+            t = age + 1
+            host[i, 0] = lr / (1.0 - b1 ** t)
+            host[i, 1] = 1.0 / math.sqrt(1.0 - b2 ** t)
+
     _HYPER_SLOTS = 8
+    _HYPER_COLS = 2
     _HYPER_ROWS = 64  # rows of the device table (one per run; a handful in practice): re-derived runs keep the allocation
 
     @torch.no_grad()
@@ -151,6 +161,9 @@ class FlatAdam(torch.optim.Optimizer):
         from grit_amd import lib as _lib
         from grit_amd.ops import backend
         lr, b1, b2, eps = self._hyper()
+        if getattr(self._owner, '_clip', None) is not None:
+            raise RuntimeError("FlatAdam: a clip factor is pending (Bf16Compute.clip_grad_norm_) and this kernel cannot apply it: "
+                               "clipped steps are taken by FlatAdamW (Bf16Compute.flat_adamw)")
         if self._layout_version != self._owner.ddp.layout_version:  # the live parameter set changed: parameters without a
             self._derive_runs()                                       # gradient are not stepped (torch.optim.Adam skips them)
         grad_scale = 1.0 / self._owner.ddp.world  # the buckets hold the SUM over ranks: the average is folded in here
@@ -220,6 +233,97 @@ class FlatAdam(torch.optim.Optimizer):
         weights_epoch.bump()  # the compute weights were rewritten by a raw kernel: no version counter saw it
 
 
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW (decoupled weight decay, amsgrad off) over the flat training state of Bf16Compute: one
+    grit_adamw_flat_dev launch per contiguous run.  Parameter groups may differ in `lr` and `weight_decay` (the detector's four
+    groups, reference train_detector.py:24-89); `betas` and `eps` are shared.  A run never mixes groups or ages: the runs are
+    derived with the key (steps taken, group index).
+
+    The per-step scalars of a run ALWAYS come from the device table: prepare_replay() writes one 16-byte row
+    {lr / bias_correction1, 1 / sqrt(bias_correction2), 1 - lr * weight_decay, 0} per run from the groups' CURRENT lr, so a
+    scheduler that rewrites param_groups[i]['lr'] is honoured at the next step.  When Bf16Compute.clip_grad_norm_ was called in
+    this step the launches read the gradient factor from its clip cell (device memory) instead of 1 / world.
+
+    `state` / `param_groups` / `state_dict()` have torch.optim.AdamW's layout: a state dict of torch.optim.AdamW over the same
+    masters loads, and the reverse."""
+
+    device_hyper = True
+    _HYPER_COLS = 4
+
+    def __init__(self, owner, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        # torch.optim.AdamW's own defaults (their key set differs between torch versions), taken from a throw-away instance
+        defaults = dict(torch.optim.AdamW([torch.zeros(1, requires_grad=True)], lr=lr, betas=betas, eps=eps,
+                                          weight_decay=weight_decay).defaults)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self._attach(owner)
+
+    def _keyed_runs(self):
+        group_of = {p: i for i, g in enumerate(self.param_groups) for p in g['params']}
+        keyed = self._owner._runs(self._mine, key=lambda p: (self._steps.get(p), group_of.get(p)))
+        self._run_group = [k[1] for _, _, k in keyed]
+        return [(run, params, k[0]) for run, params, k in keyed]
+
+    def _hyper(self):
+        shared = {(tuple(g['betas']), g['eps'], bool(g.get('amsgrad', False)), bool(g.get('maximize', False)))
+                  for g in self.param_groups}
+        if len(shared) != 1:
+            raise NotImplementedError("FlatAdamW: the parameter groups of one optimizer must share betas / eps "
+                                      "(they may differ in lr and weight_decay)")
+        (b1, b2), eps, amsgrad, maximize = next(iter(shared))
+        if amsgrad or maximize:
+            raise NotImplementedError("FlatAdamW implements AdamW with amsgrad = False, maximize = False")
+        return float(b1), float(b2), float(eps)
+
+    def _fill_hyper(self, host):
+        b1, b2, _ = self._hyper()
+        for i, (_, _, age) in enumerate(self._runs):
+            g = self.param_groups[self._run_group[i]]
+            lr, t = float(g['lr']), age + 1
+            host[i, 0] = lr / (1.0 - b1 ** t)
+            host[i, 1] = 1.0 / math.sqrt(1.0 - b2 ** t)
+            host[i, 2] = 1.0 - lr * float(g['weight_decay'])
+            host[i, 3] = 0.0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from grit_amd import lib as _lib
+        from grit_amd.ops import backend
+        b1, b2, eps = self._hyper()
+        if self._layout_version != self._owner.ddp.layout_version:  # the live parameter set changed
+            self._derive_runs()
+        grad_scale = 1.0 / self._owner.ddp.world  # the buckets hold the SUM over ranks; a pending clip cell replaces this factor
+        ov = backend.override()
+        kernel = getattr(ov, 'adamw_flat', None) if ov is not None else None  # tests on CPU inject the torch restatement
+        lib = _lib.load() if kernel is None else None
+        capturing = kernel is None and torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self.prepare_replay()
+        elif getattr(self, '_hyper_host', None) is None:
+            raise RuntimeError("FlatAdamW: call prepare_replay() once before capturing a step (the device table of the per-step "
+                               "scalars must exist before the capture begins)")
+        clip = getattr(self._owner, '_clip', None)  # {total_norm, clip_scale, clip_coef} of this step, or None
+        for i, ((bucket, compute, master, mom, var, start, end), params, age) in enumerate(self._runs):
+            n = end - start
+            if n <= 0:
+                continue
+            if kernel is not None:
+                kernel(master[start:end], bucket.flat[start:end], mom[start:end], var[start:end], compute[start:end], b1, b2, eps,
+                       grad_scale, self._hyper_dev[i], None if clip is None else clip[1])
+                continue
+            _lib.require_device(master)
+            with _lib.device_guard(master.device):
+                st = lib.grit_adamw_flat_dev(
+                    ctypes.c_void_p(master[start:].data_ptr()), ctypes.c_void_p(bucket.flat[start:].data_ptr()),
+                    int(bucket.flat.dtype == torch.bfloat16), ctypes.c_void_p(mom[start:].data_ptr()),
+                    ctypes.c_void_p(var[start:].data_ptr()), ctypes.c_void_p(compute[start:].data_ptr()), n, b1, b2, eps,
+                    grad_scale, ctypes.c_void_p(self._hyper_dev[i].data_ptr()),
+                    None if clip is None else ctypes.c_void_p(clip[1:].data_ptr()), _lib.current_stream_ptr())
+            _lib.check(st, "grit_adamw_flat_dev")
+        if not capturing:
+            self.advance()
+        return None
+
+
 class Bf16Compute(nn.Module):
 
     def __init__(self, module, bucket_mb=64, process_group=None, flat_optimizer=None, shard_optimizer=False):
@@ -252,6 +356,8 @@ class Bf16Compute(nn.Module):
                                         shard_grads=self.shard_optimizer)
         self._gather_work = []         # all-gathers of the compute weights in flight (shard_optimizer)
         self._masters_current = True   # False between a sharded optimizer step and consolidate()
+        self._clip = None              # the clip cell of this step (clip_grad_norm_), cleared by after_optimizer_step()
+        self._clip_ws = None
         self.module = module
         self._masters, self._pairs, self._moment_views, self._slots = [], [], {}, []
         for b in self.ddp.buckets:
@@ -307,6 +413,72 @@ class Bf16Compute(nn.Module):
         """Optimizer factory for build_optimizers: Adam over `params` (masters, or Adam-style groups of them)."""
         return FlatAdam(self, params, lr=lr, betas=betas, eps=eps)
 
+    def flat_adamw(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        """Optimizer factory for build_optimizers_schedulers: AdamW over `params` (masters, or AdamW-style groups of them, which may
+        differ in lr and weight_decay)."""
+        return FlatAdamW(self, params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def clip_grad_norm_(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_ for gradients that lie in the flat buckets: call it after finish_gradient_sync() and
+        before the optimizers' step().  Returns the total norm (of the gradients averaged over the ranks) as a 0-d fp32 device
+        tensor; nothing is read back.  The gradients themselves are NOT rewritten: the norm and the factor that follows from it go
+        to a clip cell {total_norm, clip_scale, clip_coef} in device memory (grit_grad_norm_flat), and every FlatAdamW.step() up to
+        the next after_optimizer_step() multiplies the gradients by clip_scale = clip_coef / world as it reads them.  A step
+        without this call is unclipped.
+
+        The ranges are the live slots of every bucket (parameters outside the live set are left out, as torch skips .grad is
+        None), INCLUDING the alignment padding between slots.  The padding is zero and stays zero: the buckets are allocated with
+        torch.zeros, every write into them goes through a parameter's view of exactly numel() elements (ddp._pack, the late path,
+        ops.linear.grad_slot), and what touches whole buffers (the collectives, the 1 / world scaling, the copy back from a wire
+        buffer) maps zeros to zeros.
+
+        With flat_optimizer=False this is torch.nn.utils.clip_grad_norm_ on the masters' fp32 .grad."""
+        if self.shard_optimizer:
+            raise NotImplementedError("clip_grad_norm_ with shard_optimizer=True: a rank holds the reduced gradients of its slice "
+                                      "only, and the cross-rank sum of squares is not implemented")
+        if not self.flat_optimizer:
+            return torch.nn.utils.clip_grad_norm_([m for _, m in self._masters], max_norm)
+        from grit_amd import lib as _lib
+        from grit_amd.ops import backend
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError("clip_grad_norm_: max_norm must be >= 0")
+        ws = self._clip_ws
+        if ws is None or ws['version'] != self.ddp.layout_version:
+            ranges = [(b.flat, start, end) for (b, _, _, _, _, start, end), _, _ in self._runs({m for _, m in self._masters})
+                      if end > start]
+            dtypes = {flat.dtype for flat, _, _ in ranges}
+            if len(dtypes) > 1 or not dtypes <= {torch.bfloat16, torch.float32}:
+                raise NotImplementedError("clip_grad_norm_: the gradient buckets must be all bf16 or all fp32")
+            dev = ranges[0][0].device if ranges else self._pairs[0][0].flat.device
+            launches = max(1, -(-len(ranges) // _lib.NORM_MAX_RANGES))
+            table = (_lib.NormRange * max(1, len(ranges)))()
+            for i, (flat, start, end) in enumerate(ranges):
+                table[i].grad = flat[start:].data_ptr()
+                table[i].n = end - start
+            ws = self._clip_ws = dict(version=self.ddp.layout_version, ranges=ranges, table=table,
+                                      partials=torch.zeros(launches * _lib.NORM_BLOCK_CAP, dtype=torch.float64, device=dev),
+                                      ticket=torch.zeros(1, dtype=torch.int32, device=dev),
+                                      out=torch.zeros(3, dtype=torch.float32, device=dev))
+        grad_scale = 1.0 / self.ddp.world
+        out, ranges = ws['out'], ws['ranges']
+        ov = backend.override()
+        kernel = getattr(ov, 'grad_norm_flat', None) if ov is not None else None  # tests on CPU inject the torch restatement
+        if not ranges:  # no live parameter: norm 0, unclipped
+            out.copy_(torch.tensor([0.0, grad_scale, 1.0]))
+        elif kernel is not None:
+            kernel([flat[start:end] for flat, start, end in ranges], grad_scale, max_norm, out)
+        else:
+            _lib.require_device(out)
+            with _lib.device_guard(out.device):
+                st = _lib.load().grit_grad_norm_flat(
+                    ws['table'], len(ranges), int(ranges[0][0].dtype == torch.bfloat16), grad_scale, max_norm,
+                    ctypes.c_void_p(ws['partials'].data_ptr()), ctypes.c_void_p(ws['ticket'].data_ptr()),
+                    ctypes.c_void_p(out.data_ptr()), _lib.current_stream_ptr())
+            _lib.check(st, "grit_grad_norm_flat")
+        self._clip = out
+        return out[0]
+
     def _runs(self, masters, key=None):
         """[(run, parameters, key value)]: maximal contiguous slot ranges of each bucket whose parameters all belong to
         `masters`, are live and share `key(parameter)` (FlatAdam: the number of steps taken).  run = (bucket, compute, master,
@@ -350,6 +522,7 @@ class Bf16Compute(nn.Module):
                     m.grad = self._pairs[bi][3][start:start + m.numel()].view_as(m)
 
     def after_optimizer_step(self):
+        self._clip = None  # the clip factor belonged to this step's gradients
         if not self.flat_optimizer:
             for b, compute_flat, master_flat, _, _, _ in self._pairs:
                 compute_flat.copy_(master_flat)  # fp32 -> bf16

@@ -83,7 +83,7 @@ _DETECTION_DEFAULTS = {
                                   eos_coef=0.1, focal_alpha=0.25),
                         matcher=dict(set_cost_class=2.0, set_cost_bbox=5.0, set_cost_giou=2.0))),
     'optimizer': dict(lr=1e-5, lr_backbone=2e-5, batch_size=4, weight_decay=1e-4, lr_drop_epochs=[40], scheduler='step',
-                      decay_rate=0.1, clip_max_norm=0.1, num_workers=4, num_epochs=50),
+                      decay_rate=0.1, clip_max_norm=0.1, num_workers=4, num_epochs=50, sp_lr=1e-4, sp_lr_drop_epochs=[5]),
 }
 
 

@@ -1,5 +1,7 @@
-"""One optimisation step of detector pre-training (reference engine/det_solver.py:58-110, without its hook machinery)."""
+"""One optimisation step of detector pre-training (reference engine/det_solver.py:58-110, without its hook machinery) and the
+optimizers it is taken with (reference train_detector.py:24-89)."""
 import torch
+from torch.optim.lr_scheduler import MultiStepLR
 
 
 def weighted_loss(loss_dict, weight_dict):
@@ -7,16 +9,83 @@ def weighted_loss(loss_dict, weight_dict):
     return sum(loss_dict[k] * weight_dict[k] for k in loss_dict if k in weight_dict)
 
 
+def _is_wrapper(model):
+    from grit_amd.amp import Bf16Compute
+    return isinstance(model, Bf16Compute)
+
+
+def build_optimizers_schedulers(model, config):
+    """The reference's rule: AdamW over four groups -- head and backbone ('backbone' in the name), each with and without weight
+    decay (1-D parameters, names ending in '.bias' and names whose last component is on the skip list are not decayed; the skip
+    list is backbone.no_weight_decay() when the backbone has it, else ['query_embed']) -- with lr / lr_backbone / weight_decay of
+    config.optimizer; a second AdamW at sp_lr for the parameters whose name contains one of config.optimizer.sp_names, when there
+    are any; one MultiStepLR (lr_drop_epochs / sp_lr_drop_epochs, decay_rate) per optimizer.  Empty groups are dropped.
+
+    For a grit_amd.amp.Bf16Compute wrapper the groups hold its fp32 masters and the optimizers are its flat AdamW
+    (Bf16Compute.flat_adamw); for a plain module they are torch.optim.AdamW.  Returns (optimizers, lr_schedulers)."""
+    wrapped = _is_wrapper(model)
+    inner = model.module if wrapped else model
+    backbone = getattr(inner, 'backbone', None)
+    skip = backbone.no_weight_decay() if hasattr(backbone, 'no_weight_decay') else ['query_embed']
+    named = model.named_master_parameters() if wrapped else [(n, p) for n, p in inner.named_parameters() if p.requires_grad]
+    opt = config.optimizer
+    sp_names = list(getattr(opt, 'sp_names', None) or [])
+    head, det_no_decay, backbone_decay, backbone_no_decay, sp_params = [], [], [], [], []
+    for name, param in named:
+        if any(ns in name for ns in sp_names):
+            sp_params.append(param)
+            continue
+        no_decay = len(param.shape) == 1 or name.endswith(".bias") or name.split('.')[-1] in skip
+        if "backbone" in name:
+            (backbone_no_decay if no_decay else backbone_decay).append(param)
+        else:
+            (det_no_decay if no_decay else head).append(param)
+    groups = [{"params": head, "lr": opt.lr, "weight_decay": opt.weight_decay},
+              {"params": det_no_decay, "lr": opt.lr, "weight_decay": 0.},
+              {"params": backbone_no_decay, "lr": opt.lr_backbone, "weight_decay": 0.},
+              {"params": backbone_decay, "lr": opt.lr_backbone, "weight_decay": opt.weight_decay}]
+    groups = [g for g in groups if g["params"]]
+
+    def adamw(params, lr):
+        if wrapped:
+            return model.flat_adamw(params, lr=lr, weight_decay=opt.weight_decay)
+        return torch.optim.AdamW(params, lr=lr, weight_decay=opt.weight_decay)
+
+    optimizers, drops = [], []
+    if groups:
+        optimizers.append(adamw(groups, opt.lr))
+        drops.append(opt.lr_drop_epochs)
+    if sp_params:
+        optimizers.append(adamw(sp_params, opt.sp_lr))
+        drops.append(opt.sp_lr_drop_epochs)
+    schedulers = [MultiStepLR(o, list(d), gamma=opt.decay_rate) for o, d in zip(optimizers, drops)]
+    return optimizers, schedulers
+
+
 def train_step(model, criterion, optimizer, samples, targets, max_norm=0.1):
     """forward -> criterion -> weighted sum over criterion.weight_dict -> backward -> gradient clipping (max_norm > 0) -> step.
+    `optimizer` is one optimizer or a list of them.  With a grit_amd.amp.Bf16Compute wrapper the gradients lie in its flat bf16
+    buckets: backward -> finish_gradient_sync() -> clip_grad_norm_(max_norm) (norm and clip factor stay on the device) -> every
+    optimizer's step() -> after_optimizer_step().
     Returns (total, loss_dict): device tensors, nothing is read back here."""
+    optimizers = list(optimizer) if isinstance(optimizer, (list, tuple)) else [optimizer]
     model.train()
     criterion.train()
     loss_dict = criterion(model(samples), targets)
     total = weighted_loss(loss_dict, criterion.weight_dict)
-    optimizer.zero_grad(set_to_none=True)
+    for o in optimizers:
+        o.zero_grad(set_to_none=True)
     total.backward()
-    if max_norm and max_norm > 0:
-        torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_norm)
-    optimizer.step()
+    if _is_wrapper(model):
+        model.finish_gradient_sync()
+        if max_norm and max_norm > 0:
+            model.clip_grad_norm_(max_norm)
+        for o in optimizers:
+            o.step()
+        model.after_optimizer_step()
+    else:
+        if max_norm and max_norm > 0:
+            torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], max_norm)
+        for o in optimizers:
+            o.step()
     return total.detach(), {k: v.detach() for k, v in loss_dict.items()}

@@ -10,7 +10,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgrit_hip.so")
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 _c = ctypes
 _ptr, _int, _i64, _f32, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -60,6 +60,8 @@ SIGNATURES = {
     "grit_groupnorm_tokens_bwd": [_ptr, _c.c_long, _ptr, _c.c_long, _ptr, _ptr, _ptr, _int, _int, _int, _int, _int, _int] + [_ptr] * 5,
     "grit_adam_flat": [_ptr, _ptr, _int, _ptr, _ptr, _ptr, _c.c_long] + [_f32] * 7 + [_ptr],
     "grit_adam_flat_dev": [_ptr, _ptr, _int, _ptr, _ptr, _ptr, _c.c_long] + [_f32] * 4 + [_ptr, _ptr],
+    "grit_adamw_flat_dev": [_ptr, _ptr, _int, _ptr, _ptr, _ptr, _c.c_long] + [_f32] * 4 + [_ptr, _ptr, _ptr],
+    "grit_grad_norm_flat": [_ptr, _int, _int, _f32, _f32, _ptr, _ptr, _ptr, _ptr],
     "grit_resample_taps_bicubic": [_int, _int, _ptr, _ptr, _c.c_long],
     "grit_image_batch_fwd": [_ptr] * 5 + [_int] * 6 + [_ptr] * 3,
     "grit_image_batch_aug_fwd": [_ptr] * 6 + [_int, _ptr, _c.c_long, _ptr] + [_int] * 7 + [_ptr] * 3,
@@ -108,6 +110,15 @@ SIGNATURES = {
 DET_MAX_SIDE = 512  # GRIT_DET_MAX_SIDE
 DET_LOSS_ROWS = 20  # GRIT_DET_LOSS_ROWS
 DET_LOSS_FIELDS = 8  # GRIT_DET_LOSS_FIELDS
+
+NORM_MAX_RANGES = 64  # GRIT_NORM_MAX_RANGES
+NORM_BLOCK_CAP = 2048  # GRIT_NORM_BLOCK_CAP
+
+
+class NormRange(_c.Structure):
+    """grit_norm_range of include/grit_hip.h."""
+    _fields_ = [("grad", _c.c_void_p), ("n", _c.c_long)]
+
 
 SLAB_GROUP_MAX = 48  # GRIT_SLAB_GROUP_MAX
 WGRAD_GROUP_MAX = 32  # GRIT_WGRAD_GROUP_MAX

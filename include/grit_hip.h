@@ -27,6 +27,9 @@
  *                           models/detection/det_module.py:172-175
  *   grit_colsum, grit_slab_sum <- bias / weight gradient reductions of nn.Linear's backward on the long token maps
  *   grit_adam_flat       <- the two torch.optim.Adam of build_optimizers, engine/caption_engine.py:18-73
+ *   grit_adamw_flat_dev, grit_grad_norm_flat
+ *                        <- torch.optim.AdamW of build_optimizers_schedulers, train_detector.py:24-89, and
+ *                           torch.nn.utils.clip_grad_norm_, engine/det_solver.py:108
  *   grit_resample_taps_bicubic, grit_image_batch_fwd
  *                        <- the image side of the batch contract: PIL resize(BICUBIC) of MaxWHResize / MinMaxResize
  *                           (datasets/caption/transforms/utils.py:4-45), ToTensor + Normalize
@@ -63,7 +66,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 50
+#define GRIT_ABI_VERSION 51
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -500,6 +503,39 @@ int grit_adam_flat(float* param, const void* grad, int grad_is_bf16, float* exp_
  * the host rewrites hyper before every replay, so the learning-rate schedule and the step count advance without a re-capture. */
 int grit_adam_flat_dev(float* param, const void* grad, int grad_is_bf16, float* exp_avg, float* exp_avg_sq, void* compute_bf16,
                        long n, float beta1, float beta2, float eps, float grad_scale, const float* hyper, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * AdamW and gradient clipping for detector pre-training on the same flat layout (ABI 51; torch.optim.AdamW of the reference's
+ * build_optimizers_schedulers, train_detector.py:24-89; torch.nn.utils.clip_grad_norm_ of engine/det_solver.py:108).
+ *
+ * grit_grad_norm_flat: the global L2 norm of n_ranges flat gradient ranges (a HOST table; all bf16, grad_is_bf16, or all f32) and
+ * the clip factor that follows from it, written to DEVICE memory and never read back:
+ *     out[0] total_norm = float(grad_scale * sqrt(sum g^2))       squares and sums in float64
+ *     out[1] clip_scale = grad_scale * clip_coef                  the factor grit_adamw_flat_dev multiplies every gradient element by
+ *     out[2] clip_coef  = min(1, max_norm / (total_norm + 1e-6))  fp32, torch's expression; a NaN gradient gives three NaNs
+ * Deterministic: one float64 partial per workgroup, added in index order by the workgroup that takes the last ticket; the entry
+ * point zeroes the ticket on the stream in front of the launches, no state outlives a call.  More than GRIT_NORM_MAX_RANGES ranges
+ * are taken by a chain of launches, the last of which finalises.
+ *   partials  f64 [GRIT_NORM_BLOCK_CAP * ceil(n_ranges / GRIT_NORM_MAX_RANGES)] workspace;  ticket  one unsigned int
+ * Every range: n % 4 == 0, bf16 pointers 8-byte, f32 pointers 16-byte aligned (GRIT_ERR_UNSUPPORTED otherwise); null pointers,
+ * n <= 0, n_ranges <= 0 or max_norm < 0: GRIT_ERR_BAD_ARG.
+ *
+ * grit_adamw_flat_dev: grit_adam_flat_dev behind  p <- p * hyper[2]  (decoupled weight decay, torch's order).  hyper is a 16-byte
+ * aligned row of four floats {lr / bias_correction1, 1 / bias_correction2_sqrt, 1 - lr * weight_decay, unused}.  clip_scale may be
+ * NULL; otherwise the kernel multiplies the gradients by *clip_scale (out + 1 of grit_grad_norm_flat) in place of grad_scale.
+ * hyper[2] == 1 and clip_scale == NULL: bit-identical to grit_adam_flat_dev.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_NORM_MAX_RANGES 64
+#define GRIT_NORM_BLOCK_CAP 2048 /* workgroups (of 256 threads, one 16-byte load each) one pass of the capped grid holds */
+typedef struct grit_norm_range {
+    const void* grad;
+    long n;
+} grit_norm_range;
+int grit_grad_norm_flat(const grit_norm_range* ranges, int n_ranges, int grad_is_bf16, float grad_scale, float max_norm,
+                        double* partials, unsigned int* ticket, float* out, void* stream);
+int grit_adamw_flat_dev(float* param, const void* grad, int grad_is_bf16, float* exp_avg, float* exp_avg_sq, void* compute_bf16,
+                        long n, float beta1, float beta2, float eps, float grad_scale, const float* hyper, const float* clip_scale,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Decoded RGB images -> the model's input batch: bicubic resize with Pillow's 8-bit arithmetic

@@ -1,10 +1,12 @@
 """Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
 
-    python train_detector.py --synthetic --steps 3 [--batch-size 2] [--size 224] [key=value ...]
+    python train_detector.py --synthetic --steps 3 [--batch-size 2] [--size 224] [--bf16] [key=value ...]
 
 The Visual Genome / LMDB readers, the hook-based solver and the COCO-style evaluation are out of scope of this build, so the only
 data source here is `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
 (grit_amd/models/detection/od_losses.py) and engine.det_engine.train_step, and prints the loss dictionary of every step.
+`--bf16` trains on the path the captioner uses (grit_amd.amp.Bf16Compute: bf16 compute copies, fp32 masters, flat AdamW and gradient
+clipping on the device, the reference's four parameter groups and MultiStepLR; engine.det_engine.build_optimizers_schedulers).
 Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
 """
 import argparse
@@ -12,7 +14,7 @@ import argparse
 import torch
 
 from grit_amd.config import detection_config
-from engine.det_engine import train_step
+from engine.det_engine import build_optimizers_schedulers, train_step
 from models.detection.detector import build_detector
 from utils.misc import NestedTensor
 
@@ -38,6 +40,9 @@ def main():
     ap.add_argument('--batch-size', type=int, default=None)
     ap.add_argument('--size', type=int, default=224, help='image side')
     ap.add_argument('--max-targets', type=int, default=30)
+    ap.add_argument('--bf16', action='store_true', help='bf16 compute + fp32 masters: flat AdamW and device gradient clipping')
+    ap.add_argument('--steps-per-epoch', type=int, default=0,
+                    help='with --bf16: step the lr schedulers once per this many steps (0: never within a run)')
     ap.add_argument('overrides', nargs='*', help='dotted key=value configuration overrides')
     args = ap.parse_args()
     if not args.synthetic:
@@ -58,16 +63,29 @@ def main():
     device = torch.device('cuda')
     model, criterion, _ = build_detector(config)
     model.to(device)
-    backbone = [p for n, p in model.named_parameters() if n.startswith('backbone.') and p.requires_grad]
-    rest = [p for n, p in model.named_parameters() if not n.startswith('backbone.') and p.requires_grad]
-    optimizer = torch.optim.AdamW([{'params': rest, 'lr': config.optimizer.lr}, {'params': backbone, 'lr': config.optimizer.lr_backbone}],
-                                  weight_decay=config.optimizer.weight_decay)
+    schedulers = []
+    if args.bf16:
+        from grit_amd.amp import Bf16Compute
+        model = Bf16Compute(model)
+        optimizer, schedulers = build_optimizers_schedulers(model, config)
+    else:
+        optimizer = _plain_optimizer(model, config)
     g = torch.Generator().manual_seed(config.exp.seed)
     batch_size = args.batch_size or config.optimizer.batch_size
     for step in range(args.steps):
         samples, targets = synthetic_batch(g, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
         total, losses = train_step(model, criterion, optimizer, samples, targets, config.optimizer.clip_max_norm)
         print('step %d  loss %.5f  %s' % (step, float(total), {k: round(float(v), 5) for k, v in sorted(losses.items())}))
+        if args.steps_per_epoch > 0 and (step + 1) % args.steps_per_epoch == 0:
+            for sch in schedulers:
+                sch.step()
+
+
+def _plain_optimizer(model, config):
+    backbone = [p for n, p in model.named_parameters() if n.startswith('backbone.') and p.requires_grad]
+    rest = [p for n, p in model.named_parameters() if not n.startswith('backbone.') and p.requires_grad]
+    return torch.optim.AdamW([{'params': rest, 'lr': config.optimizer.lr}, {'params': backbone, 'lr': config.optimizer.lr_backbone}],
+                             weight_decay=config.optimizer.weight_decay)
 
 
 if __name__ == '__main__':
