@@ -26,8 +26,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
-import ctypes
-
 from grit_amd import lib as _lib
 from grit_amd.ops import backend as _backend
 from grit_amd.ops.layer_norm import LayerNorm, add_layer_norm, linear_add_layer_norm, merge_layer_norm
@@ -432,12 +430,12 @@ class PatchEmbed(nn.Module):
         B, _, H, W = x.shape
         out = torch.empty((B, (H // 4) * (W // 4), self.embed_dim), dtype=torch.bfloat16, device=x.device)
         w2 = w.view(self.embed_dim, 48)
-        ptr = lambda t_: ctypes.c_void_p(t_.data_ptr())
+        ptr = _lib.ptr
         with _lib.device_guard(x.device):
             st = _lib.load().grit_patch_embed_ln_fwd(ptr(x), int(x.dtype == torch.bfloat16), B, H, W, self.embed_dim, ptr(w2), ptr(self.proj.bias),
                                                      ptr(self.norm.weight), ptr(self.norm.bias), float(self.norm.eps), ptr(out),
                                                      _lib.current_stream_ptr())
-        if st == 2:  # GRIT_ERR_UNSUPPORTED (shape outside the kernel): the GEMM path
+        if st == _lib.ERR_UNSUPPORTED:  # shape outside the kernel: the GEMM path
             return None
         _lib.check(st, "grit_patch_embed_ln_fwd")
         return out

@@ -9,7 +9,6 @@ kept per row (log-sum-exp) so the backward recomputes P instead of storing [B,H,
 Dropout on P uses a counter-based hash RNG keyed by (seed, b, h, q, k): the backward regenerates the same
 keep-mask from the seed saved in the autograd context.
 """
-import ctypes
 import math
 
 import torch
@@ -22,8 +21,7 @@ from grit_amd.ops import backend
 HEAD_DIM = 64  # d_k of every attention on GRIT's path (d_model 512 / 8 heads)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def _rows(t):

@@ -10,8 +10,7 @@ from grit_amd import lib as _lib
 from grit_amd.ops import backend
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def supported(word_logprob, cur_beam, beam_size):

@@ -101,7 +101,7 @@ class DeviceCaptionScorer(object):
         rouge = torch.empty(N, dtype=torch.float64, device=self.device)
         cider = torch.empty(N, dtype=torch.float64, device=self.device)
         L = _lib.load()
-        p = lambda x: ctypes.c_void_p(x.data_ptr())
+        p = _lib.ptr
         with _lib.device_guard(self.device):
             st = L.grit_caption_scores(p(tok), N, T, p(index), 1 if collapse else 0,
                                        ctypes.c_void_p(ctypes.addressof(self.tables._table_struct())),

@@ -1,7 +1,6 @@
 """Inputs of one step of step-wise decoding as one launch (grit_decode_step_inputs, include/grit_hip.h): the pad / key masks, the step
 counter and the word + position embedding sum of CaptionGenerator.get_seq_inputs in stateful mode (reference
 models/caption/cap_generator.py:116-137,148)."""
-import ctypes
 
 import torch
 
@@ -9,8 +8,7 @@ from grit_amd import lib as _lib
 from grit_amd.ops import backend
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def supported(tokens, word_emb, pos_emb, running_seq, running_mask):

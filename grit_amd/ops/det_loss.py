@@ -5,7 +5,6 @@ This module is the host side: it packs the targets, allocates the per-call works
 Nothing here reads a device value back: the target counts are the shapes of the target tensors, known to the host; the offsets
 and the box count travel through pinned memory with a non-blocking copy.
 """
-import ctypes
 
 import torch
 
@@ -15,8 +14,7 @@ from grit_amd.utils.misc import get_world_size, is_dist_avail_and_initialized
 FIELDS = _lib.DET_LOSS_FIELDS
 LOSS_CE, LOSS_BBOX, LOSS_GIOU, CARDINALITY_ERROR, CLASS_ERROR = range(5)  # columns of the criterion's [L, FIELDS] output
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_p = _lib.ptr
 
 
 class PackedTargets(object):

@@ -1,7 +1,6 @@
 """Sigmoid-gated merge of the two cross-attentions of a caption decoder layer at inference (reference
 models/caption/cap_generator.py:44-56) in three launches -- grit_gate_pack, ONE fc_alpha1 GEMM on the stacked inputs,
 grit_gate_fuse -- instead of fourteen, with the composed form's roundings (include/grit_hip.h)."""
-import ctypes
 
 import numpy as np
 import torch
@@ -11,8 +10,7 @@ from grit_amd import lib as _lib
 from grit_amd.ops import backend
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def supported(self_att, enc1, enc2, mask_pad, fc):

@@ -4,7 +4,6 @@
 (GEMM + bias + exact GELU; the pre-activation is kept for the backward) and a backward whose input-gradient GEMM of the
 *following* Linear already multiplies by GELU' and sums the bias gradient (`Fc2InputGrad`), so no GELU / GeluBackward /
 column-sum kernel touches the [M, 4C] hidden map."""
-import ctypes
 import os
 
 import torch
@@ -12,15 +11,12 @@ import torch
 from grit_amd import lib as _lib
 from grit_amd.ops.profiling import gemm_work, timed
 
-NONE, BIAS, BIAS_GELU, DGELU = 0, 1, 2, 3
+NONE, BIAS, BIAS_GELU, DGELU = _lib.GEMM_NONE, _lib.GEMM_BIAS, _lib.GEMM_BIAS_GELU, _lib.GEMM_DGELU  # epilogues of grit_gemm_bf16_nt
 # GRIT_GEMM_ROW_SKIP (default 1): the fc2 input gradient skips the tiles of samples that drop path removed from the branch (exact zeros)
 ROW_SKIP = os.environ.get("GRIT_GEMM_ROW_SKIP", "1") != "0"
-COLSUM_ROWS = 128
+COLSUM_ROWS = _lib.GEMM_COLSUM_ROWS
 VARIANT = int(os.environ.get("GRIT_GEMM_VARIANT", "0"))  # tuning alternatives of the same kernel (A/B runs)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def supported(x2, weight):
@@ -49,7 +45,7 @@ def gemm_nt(a, b, epilogue=NONE, bias=None, aux=None, colsum=None, out=None, var
     return out
 
 
-BIAS_RELU_DROP, DRELU = 5, 6  # grit_gemm_bf16_nt_relu
+BIAS_RELU_DROP, DRELU = _lib.GEMM_BIAS_RELU_DROP, _lib.GEMM_DRELU  # grit_gemm_bf16_nt_relu
 
 
 def gemm_nt_relu(a, b, epilogue, bias=None, aux=None, p=0.0, seed_dev=None):

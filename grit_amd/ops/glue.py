@@ -8,7 +8,6 @@ composed torch form when its kernel does not apply (CPU / oracle runs, unusual d
   relu_dropout        dropout(relu(x)) of the position-wise FFNs            det_module.py:302-304, models/common/pos_embed.py:44-48
   gated_merge_train   sigmoid-gated merge of the two cross-attentions       models/caption/cap_generator.py:44-56
 """
-import ctypes
 import os
 
 import numpy as np
@@ -23,8 +22,7 @@ from grit_amd.ops import backend
 ENABLED = os.environ.get("GRIT_FUSED_GLUE", "1") != "0"
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def _on_device(*ts):

@@ -5,7 +5,6 @@
 One autograd node for all levels: forward = 2 launches per level (grit_groupnorm_tokens_fwd), no NCHW permute, no
 torch.cat; backward reads the gradient of the flat map slice by slice.  Reference: models/caption/detector.py:28-33,58
 (Conv2d 1x1 + GroupNorm(32, hidden_dim) per level) and models/detection/det_module.py:172-175 (flatten + cat)."""
-import ctypes
 
 import torch
 import torch.nn.functional as F
@@ -15,11 +14,8 @@ from torch.autograd.function import once_differentiable
 from grit_amd import lib as _lib
 from grit_amd.ops import backend
 
-GN_CHUNKS = 16  # GRIT_GN_CHUNKS in include/grit_hip.h
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+GN_CHUNKS = _lib.GN_CHUNKS
+_ptr = _lib.ptr
 
 
 class _GroupNormLevelsFn(Function):

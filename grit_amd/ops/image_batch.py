@@ -28,14 +28,11 @@ from grit_amd import lib as _lib
 
 MEAN = (0.485, 0.456, 0.406)  # transforms/__init__.py:6-7
 STD = (0.229, 0.224, 0.225)
-DESC_FIELDS = 12  # GRIT_IMAGE_DESC_FIELDS
-SRC_PAD = 64  # GRIT_IMAGE_SRC_PAD
-
-
-AUG_STAGES = 4  # GRIT_IMAGE_AUG_STAGES
-AUG_FIELDS = 36  # GRIT_IMAGE_AUG_FIELDS
-AUG_COPY, AUG_AUTOCONTRAST, AUG_AFFINE_FIXED, AUG_AFFINE_TABLE = 0, 1, 2, 3  # GRIT_AUG_*
-AUG_BLEND = {'Color': 4, 'Contrast': 5, 'Brightness': 6, 'Sharpness': 7}
+DESC_FIELDS, SRC_PAD = _lib.IMAGE_DESC_FIELDS, _lib.IMAGE_SRC_PAD
+AUG_STAGES, AUG_FIELDS = _lib.IMAGE_AUG_STAGES, _lib.IMAGE_AUG_FIELDS
+AUG_COPY, AUG_AUTOCONTRAST, AUG_AFFINE_FIXED, AUG_AFFINE_TABLE = (_lib.AUG_COPY, _lib.AUG_AUTOCONTRAST, _lib.AUG_AFFINE_FIXED,
+                                                                  _lib.AUG_AFFINE_TABLE)
+AUG_BLEND = {'Color': _lib.AUG_COLOR, 'Contrast': _lib.AUG_CONTRAST, 'Brightness': _lib.AUG_BRIGHTNESS, 'Sharpness': _lib.AUG_SHARPNESS}
 
 
 def tmp_pitch(dst_w):
@@ -278,7 +275,7 @@ def image_batch(images, sizes, mean=MEAN, std=STD, device=None, pad_to=None, aug
         tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=device)
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
         mask = torch.empty(B, H, W, dtype=torch.bool, device=device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = _lib.ptr
         if augment is not None:
             work = torch.empty(2 * work_bytes, dtype=torch.uint8, device=device)
             blocks = ((max_dst_h * ((max_dst_w + 3) // 4) + 255) // 256 + 7) // 8 * 8  # GRIT_IMAGE_AUG_BLOCKS

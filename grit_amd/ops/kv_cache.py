@@ -1,14 +1,12 @@
 """Key / value cache of step-wise decoding under beam search as one launch per layer and step (grit_kv_append, include/grit_hip.h):
 the surviving beams take over their source beam's history and the new token's projected key / value is appended."""
-import ctypes
 
 import torch
 
 from grit_amd import lib as _lib
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def append(old_k, old_v, src_beam, new_k, new_v, beam):

@@ -3,7 +3,6 @@
 Used by the Swin backbone (norm1 / norm2 / patch-merging / patch-embed norms): there LayerNorm is a pure HBM
 stream over maps of up to 819 200 tokens and torch's bf16 kernels run at a fraction of the bandwidth.  A device tensor
 whose channel count / dtype the kernels do not cover RAISES (no silent library fallback on the hot path)."""
-import ctypes
 
 import torch
 import torch.nn.functional as F
@@ -18,11 +17,8 @@ from grit_amd.ops.linear import (SlabGroup, _own_linear, _rows, defer_slab_group
 from grit_amd.ops.profiling import gemm_work, timed
 
 SUPPORTED_C = (128, 256, 512, 1024, 2048, 4096)
-LN_BWD_PARTIALS = 1024  # GRIT_LN_BWD_PARTIALS in include/grit_hip.h
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+LN_BWD_PARTIALS = _lib.LN_BWD_PARTIALS
+_ptr = _lib.ptr
 
 
 class _LayerNormFn(Function):

@@ -13,7 +13,6 @@ Nothing else touches the [M, 4C] hidden map: no GELU, GeluBackward or column-sum
 Without autograd at C = 128 (the frozen stage 0 of a training step, inference) the whole Mlp half of a block -- norm2, fc1 + GELU,
 fc2, the residual add and the next block's norm1 -- is ONE launch, grit_mlp_s0_fwd_bf16 (mlp_norm_residual): the hidden map never
 exists."""
-import ctypes
 import os
 
 import torch
@@ -37,8 +36,7 @@ MIN_ROWS = 2048
 S0_MLP_FUSED = os.environ.get("GRIT_S0_MLP_FUSED", "1") != "0"
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 def _mlp_backward(d_branch, n2, w1, pre, act, w2, needs, need_b2=False, group=None, params=None, row_scale=None, rows_per_sample=0):

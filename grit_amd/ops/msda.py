@@ -88,8 +88,7 @@ def _bwd_sorted(value_ptr, pixel_stride, shapes, lsi, loc, aw, go, B, S, M, D, L
     _lib.check(st, "grit_msda_bwd_bf16_sorted")
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def _algorithmic_bytes(kind, B, S, M, D, L, Lq, P, esize, geom_esize=None, grad_esize=None):

@@ -4,7 +4,6 @@
 
 Forward is one small gather kernel writing the [nH, N, N] fp32 slab the attention kernels read; backward sums d(bias)
 over the positions that share a table row, from a host-sorted position list (no atomics, no sort per step)."""
-import ctypes
 
 import torch
 from torch.autograd import Function
@@ -21,8 +20,7 @@ GROUPED_BACKWARD = os.environ.get("GRIT_GROUPED_REL_BIAS_BWD", "1") != "0"
 _SORTED = {}  # (device, n_rows, index data_ptr, numel) -> (order int32 [n_pos], offsets int32 [n_rows + 1])
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def _sorted_positions(index, n_rows):

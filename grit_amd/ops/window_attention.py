@@ -11,7 +11,6 @@ padding tokens are synthesised in-kernel from `pad_qkv` (= the Linear's bias, si
 zeros after norm1).  Gradients: dqkv, d rel_bias (summed over windows, flows on to the bias table through
 the gather in WindowAttention.relative_position_bias) and d pad_qkv.
 """
-import ctypes
 
 import torch
 from torch.autograd import Function
@@ -58,8 +57,7 @@ def _core_flops(B, nWh, nWw, num_heads, N, products):
     return products * 2 * N * N * HEAD_DIM * B * nWh * nWw * num_heads
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+_ptr = _lib.ptr
 
 
 class _WindowAttentionFn(Function):

@@ -8,26 +8,25 @@ import numpy as np
 import pytest
 import torch
 
+from grit_amd import lib as binding
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-OK, BAD_ARG, UNSUPPORTED = 0, 1, 2  # GRIT_OK, GRIT_ERR_BAD_ARG, GRIT_ERR_UNSUPPORTED (include/grit_hip.h)
+OK, BAD_ARG, UNSUPPORTED = binding.OK, binding.ERR_BAD_ARG, binding.ERR_UNSUPPORTED
 SENTINEL = -12345.0  # exactly representable in bf16 and fp32
 BF16, F32 = torch.bfloat16, torch.float32
 GUARD = 64  # elements behind n in every buffer
-NORM_MAX_RANGES = 64  # GRIT_NORM_MAX_RANGES
-NORM_BLOCK_CAP = 2048  # GRIT_NORM_BLOCK_CAP
+NORM_MAX_RANGES, NORM_BLOCK_CAP = binding.NORM_MAX_RANGES, binding.NORM_BLOCK_CAP
 NORM_PASS = NORM_BLOCK_CAP * 256  # 16-byte units (8 bf16 or 4 fp32 elements) one pass of the capped grid covers
 ADAM_BLOCK_CAP = 8192 * 256  # quads one pass of the capped Adam grid covers
 LR, BETA1, BETA2, ADAM_EPS = 1e-2, 0.9, 0.999, 1e-8
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+_ptr = binding.ptr
 
 
 def _lib():
-    from grit_amd import lib
-    return lib.load(), lib.current_stream_ptr()
+    return binding.load(), binding.current_stream_ptr()
 
 
 def _f32(v):
@@ -44,9 +43,8 @@ def _ulps(a, b):
 
 
 def test_constants_match_the_binding():
-    from grit_amd import lib
-    assert (lib.NORM_MAX_RANGES, lib.NORM_BLOCK_CAP, lib.ABI_VERSION >= 51) == (NORM_MAX_RANGES, NORM_BLOCK_CAP, True)
-    assert ctypes.sizeof(lib.NormRange) == 16
+    assert binding.ABI_VERSION >= 51
+    assert ctypes.sizeof(binding.NormRange) == 16
 
 
 # ---------------------------------------------------------------------------------------------------------------- gradient norm

@@ -171,10 +171,10 @@ def test_entry_point_rejects_bad_arguments_before_any_device_work():
                                             ptrs['mask'], None)
 
     for name in ('src', 'desc', 'tables', 'tmp', 'lut', 'aug', 'work', 'stats', 'out', 'mask'):
-        assert call(null=name) == 1, name  # GRIT_ERR_BAD_ARG
+        assert call(null=name) == _lib.ERR_BAD_ARG, name
     for over in (dict(n_stages=5), dict(n_stages=-1), dict(work_bytes=0), dict(work_bytes=6), dict(batch=0), dict(max_dst_w=5),
                  dict(max_dst_h=5), dict(max_kx=0)):
-        assert call(**over) == 1, over
-    assert call(max_dst_w=40000, out_w=40000) == 2  # GRIT_ERR_UNSUPPORTED
+        assert call(**over) == _lib.ERR_BAD_ARG, over
+    assert call(max_dst_w=40000, out_w=40000) == _lib.ERR_UNSUPPORTED
     with pytest.raises(_lib.GritHipError, match="Not implemented on the CPU"):
         ib.image_batch([np.zeros((4, 4, 3), np.uint8)], [(2, 2)], device='cpu', augment=[()])

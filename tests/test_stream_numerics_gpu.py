@@ -10,22 +10,22 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from grit_amd import lib as binding
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-OK, BAD_ARG, UNSUPPORTED = 0, 1, 2  # GRIT_OK, GRIT_ERR_BAD_ARG, GRIT_ERR_UNSUPPORTED (include/grit_hip.h)
-GN_CHUNKS = 16  # GRIT_GN_CHUNKS
+OK, BAD_ARG, UNSUPPORTED = binding.OK, binding.ERR_BAD_ARG, binding.ERR_UNSUPPORTED
+GN_CHUNKS = binding.GN_CHUNKS
 EPS = 1e-5
 SENTINEL = -12345.0  # exactly representable in bf16 and fp32
 BF16, F32 = torch.bfloat16, torch.float32
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+_ptr = binding.ptr
 
 
 def _lib():
-    from grit_amd import lib
-    return lib.load(), lib.current_stream_ptr()
+    return binding.load(), binding.current_stream_ptr()
 
 
 def _close(got, want, rtol, atol, what=""):
