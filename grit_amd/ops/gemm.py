@@ -74,11 +74,15 @@ def w4_tile_rows(M, N, device=None):
 
 def gemm_nt_residual(a, b, bias, residual, row_scale=None, rows_per_sample=0, out=None):
     """out[M, N] = residual + row_scale[m // rows_per_sample] * bf16(a @ b^T + bias): the output projection of a Swin branch with its
-    residual connection in one launch (grit_gemm_bf16_nt_res); the branch map is never written.  row_scale: [B] float32 or None."""
+    residual connection in one launch (grit_gemm_bf16_nt_res); the branch map is never written.  row_scale: [B] float32 or None.
+    `out` must not share storage with `residual`: the four-wave kernel stores the rows its shifted last tile shares with the tile
+    before it twice, so in place the branch would be added twice there."""
     M, K = a.shape
     N = b.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    elif out.untyped_storage().data_ptr() == residual.untyped_storage().data_ptr():
+        raise ValueError("gemm_nt_residual: `out` shares storage with `residual` (the kernel is not in-place safe)")
     work = gemm_work(M, N, K, extra_in=1)
     with _lib.device_guard(a.device), timed("gemm_own", epilogue=4, kernel="gemm_w4" if (N % 256 == 0 and K % 64 == 0) else "gemm_nt_bf16", **work):
         st = _lib.load().grit_gemm_bf16_nt_res(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out), out.stride(0), M, N, K, _ptr(bias),

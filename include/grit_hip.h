@@ -662,7 +662,9 @@ int grit_gemm_w4_tile_rows(int M, int N);
  * -- the branch rounded to bf16 as an unfused Linear stores it, product and sum in fp32 (not fused), one rounding: bit for bit what
  * grit_add_layernorm_fwd computes as its `sum_out` from a stored branch.  row_scale NULL = 1 (then rows_per_sample is ignored);
  * otherwise rows_per_sample >= 256.  The branch map is never written or re-read.  N % 256 == 0 and K % 64 == 0: variant 7's kernel and
- * shape limits; other N % 128 == 0, K % 32 == 0 (the 128 output columns of the stage-0 map): the per-tile kernel on 256 x 128 tiles. */
+ * shape limits; other N % 128 == 0, K % 32 == 0 (the 128 output columns of the stage-0 map): the per-tile kernel on 256 x 128 tiles.
+ * C must not overlap residual: the four-wave kernel shifts its last row tile back to end at row M and computes and stores the rows it
+ * shares with the tile before it twice -- in place the branch would be added twice there. */
 int grit_gemm_bf16_nt_res(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                           const void* bias, const void* residual, long ldres, const float* row_scale, int rows_per_sample,
                           void* stream);
