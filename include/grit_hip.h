@@ -482,8 +482,12 @@ int grit_wgrad_tn(const void* dY, long ldy, const void* X, long ldx, int M, int 
  * per-sample keep w.p. 1 - p): row_scale[b] == 0 promises that rows [b * rows_per_sample, (b + 1) * rows_per_sample) of dY are exact
  * zeros.  Those rows add nothing to dW, so their 64-row steps are never loaded and the S slices share the LIVE steps equally (a slice is
  * a run of live steps instead of a fixed row range: the slice partials differ from grit_wgrad_tn's, their sum only by fp32 summation
- * order).  Applies on the four-wave kernel when rows_per_sample % 64 == 0 and M / rows_per_sample is 2..64; otherwise -- and with
- * GRIT_WGRAD_ROW_SKIP=0 -- every row is processed, which is equally correct.  X may hold anything in skipped rows (never read). */
+ * order).  Applies on the four-wave kernel when rows_per_sample % 64 == 0, M / rows_per_sample is 2..64, at least one sample is
+ * dropped and the kept samples hold at least `splits` 64-row steps (every slice needs one); otherwise -- fewer live steps than
+ * slices, rows_per_sample % 64 != 0, more than 64 samples, the eight-wave kernel (in a grouped launch: any job with M % 64 == 32),
+ * GRIT_WGRAD_ROW_SKIP=0 -- every row is processed, which is equally correct.  Where skipping applies the rows of X in dropped samples
+ * are never read and may hold anything; where it does not they ARE read (and multiplied by the zeros of dY), so a caller that cannot
+ * tell the two apart keeps X finite everywhere. */
 int grit_wgrad_tn_rows(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, int splits, float* partial,
                        float* db_partial, const float* row_scale, int rows_per_sample, void* stream);
 
