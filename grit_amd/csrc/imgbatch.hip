@@ -190,11 +190,18 @@ static double cubic_weight(double x) {  // bicubic convolution kernel, a = -0.5
     return 0.0;
 }
 
-extern "C" int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bounds, int32_t* taps, long taps_capacity) {
+static double triangle_weight(double x) {  // bilinear
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for a filter of half-width `radius` source pixels at scale 1
+static int resample_taps(double (*weight)(double), double radius, int in_size, int out_size, int32_t* bounds, int32_t* taps,
+                         long taps_capacity) {
     if (in_size <= 0 || out_size <= 0) return -GRIT_ERR_BAD_ARG;
     const double scale = (double)in_size / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * filterscale, inv = 1.0 / filterscale;
+    const double support = radius * filterscale, inv = 1.0 / filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     if (!bounds && !taps) return ksize;
     if (!bounds || !taps || taps_capacity < (long)out_size * ksize) return -GRIT_ERR_BAD_ARG;
@@ -209,7 +216,7 @@ extern "C" int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bo
         const int count = last - first;
         double total = 0.0;
         for (int x = 0; x < count; ++x) {
-            k[x] = cubic_weight((x + first - center + 0.5) * inv);
+            k[x] = weight((x + first - center + 0.5) * inv);
             total += k[x];
         }
         int32_t* t = taps + (long)xx * ksize;
@@ -223,6 +230,14 @@ extern "C" int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bo
     }
     if (k != stack_k) delete[] k;
     return ksize;
+}
+
+extern "C" int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bounds, int32_t* taps, long taps_capacity) {
+    return resample_taps(cubic_weight, 2.0, in_size, out_size, bounds, taps, taps_capacity);
+}
+
+extern "C" int grit_resample_taps_bilinear(int in_size, int out_size, int32_t* bounds, int32_t* taps, long taps_capacity) {
+    return resample_taps(triangle_weight, 1.0, in_size, out_size, bounds, taps, taps_capacity);
 }
 
 extern "C" int grit_image_batch_fwd(const uint8_t* src, const int64_t* desc, const int32_t* tables, uint8_t* tmp,
@@ -639,5 +654,222 @@ extern "C" int grit_image_batch_aug_fwd(const uint8_t* src, const int64_t* desc,
                            work + (i & 1) * work_bytes, work + ((i + 1) & 1) * work_bytes, stats, i);
     hipLaunchKernelGGL(normalize_pad, dim3((out_w + 1023) / 1024, out_h, batch), dim3(256), 0, s,
                        work, work_bytes, d, aug, lut, out_h, out_w, out, mask);
+    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The detector's input pipeline (reference datasets/detection/transforms.py:107-223, 240-352: hflip, resize, crop chained on
+// PIL images): grit_image_batch_geo_fwd.  An image takes one or two resizes, A then B, each over a source WINDOW: the host
+// folds a crop into the window's first byte and height and a horizontal flip into mirrored taps of the next horizontal pass
+// (sum_k tap[k] * flipped[first + k] = sum_k tap[count - 1 - k] * row[w - first - count + k], integers), so the kernels see
+// neither.  Resize A ends as uint8 rows in the work buffer (dword-aligned rows like the intermediate), resize B reads the blob
+// or that buffer and ends in the float stage of grit_image_batch_fwd.  Same arithmetic, same clip8, same lookup table.
+namespace {
+
+struct GeoResize {  // see grit_hip.h
+    int64_t buf, off, pitch, src_h, dst_h, dst_w, kx, ky, xb_off, xt_off, yb_off, yt_off, tmp_off, out_off;
+};
+struct GeoDesc {
+    int64_t n, spare;
+    GeoResize r[2];
+};
+static_assert(sizeof(GeoDesc) == GRIT_IMAGE_GEO_FIELDS * sizeof(int64_t), "geometry descriptor layout");
+
+// horizontal pass of resize `which` (0 = A, 1 = B), generic: resample_rows_any over a window
+__global__ __launch_bounds__(256)
+void geo_rows_any(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ work, const GeoDesc* __restrict__ desc,
+                  const int32_t* __restrict__ tables, uint8_t* __restrict__ tmp, int which) {
+    if (which == 0 && desc[blockIdx.z].n < 2) return;  // one-resize images sit out pass A (block-uniform)
+    const GeoResize d = desc[blockIdx.z].r[which];
+    const int y = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;  // byte within the output row
+    const int ow = (int)d.dst_w;
+    if (y >= d.src_h || j >= ow * 3) return;
+    const int xx = j / 3, c = j - xx * 3;
+    const int2 b = *reinterpret_cast<const int2*>(tables + d.xb_off + 2 * xx);
+    const int32_t* __restrict__ k = tables + d.xt_off + (int64_t)xx * d.kx;
+    const uint8_t* __restrict__ p = (d.buf ? work : blob) + d.off + (int64_t)y * d.pitch + 3 * b.x + c;
+    int ss = 1 << (kPrecisionBits - 1);
+    for (int x = 0; x < b.y; ++x) ss += (int)p[3 * x] * k[x];
+    tmp[d.tmp_off + (int64_t)y * tmp_pitch(ow) + j] = clip8(ss);
+}
+
+// horizontal pass of resize `which`, up to K taps: resample_rows_k over a window -- the same aligned-dword fetch and
+// v_alignbyte realignment, with the row address taken from the window's first byte and the source's row pitch.  A row reads
+// kWords + 1 dwords from its first tap's dword on, whatever the tap count: both source buffers carry GRIT_IMAGE_SRC_PAD
+// readable bytes past their end, and a window's first byte is never negative, so the fetch stays inside them.
+template <int K>
+__global__ __launch_bounds__(256)
+void geo_rows_k(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ work, const GeoDesc* __restrict__ desc,
+                const int32_t* __restrict__ tables, uint8_t* __restrict__ tmp, int which) {
+    constexpr int kWords = (3 * K + 3) / 4;
+    __shared__ uint32_t packed[4][kRows][48];
+    if (which == 0 && desc[blockIdx.z].n < 2) return;  // block-uniform
+    const GeoResize d = desc[blockIdx.z].r[which];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x_wave = blockIdx.x * 256 + wave * 64;
+    const int y0 = blockIdx.y * kRows;
+    const int ow = (int)d.dst_w, h = (int)d.src_h, kx = (int)d.kx;
+    if (y0 >= h || x_wave >= ow) return;  // wave-uniform
+    const int xx = min(x_wave + lane, ow - 1);
+    const int first = tables[d.xb_off + 2 * xx];
+    const int32_t* __restrict__ k = tables + d.xt_off + (int64_t)xx * kx;
+    int tap[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) tap[t] = t < kx ? k[t] : 0;
+    const int pitch = tmp_pitch(ow);
+    const uint8_t* __restrict__ src = d.buf ? work : blob;
+    uint8_t* __restrict__ staged = reinterpret_cast<uint8_t*>(&packed[wave][0][0]);
+#pragma unroll
+    for (int r = 0; r < kRows; ++r) {
+        const int y = min(y0 + r, h - 1);
+        const int64_t a = d.off + (int64_t)y * d.pitch + 3 * first;
+        const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(src + (a & ~(int64_t)3));
+        const uint32_t shift = (uint32_t)(a & 3);
+        uint32_t raw[kWords + 1], word[kWords];
+#pragma unroll
+        for (int i = 0; i <= kWords; ++i) raw[i] = q[i];
+#pragma unroll
+        for (int i = 0; i < kWords; ++i) word[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], shift);
+        int s[3] = {1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1)};
+#pragma unroll
+        for (int t = 0; t < K; ++t)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int j = 3 * t + c;
+                s[c] += __mul24((int)((word[j >> 2] >> (8 * (j & 3))) & 0xffu), tap[t]);
+            }
+        uint8_t* __restrict__ o = staged + r * 192 + 3 * lane;
+        o[0] = clip8(s[0]); o[1] = clip8(s[1]); o[2] = clip8(s[2]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int byte0 = 3 * x_wave + 4 * lane;
+    if (lane < 48 && byte0 < pitch) {
+#pragma unroll
+        for (int r = 0; r < kRows; ++r)
+            if (y0 + r < h)
+                *reinterpret_cast<uint32_t*>(tmp + d.tmp_off + (int64_t)(y0 + r) * pitch + byte0) = packed[wave][r][lane];
+    }
+}
+
+// the vertical taps of one resize on the thread's 4 pixels of output row yy: 12 sums, rounding term included
+__device__ __forceinline__ void geo_cols_quad(const uint8_t* __restrict__ tmp, const GeoResize& d, const int32_t* __restrict__ tables,
+                                              int yy, int px0, int pitch, int* s) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = 1 << (kPrecisionBits - 1);
+    const int first = tables[d.yb_off + 2 * yy], count = tables[d.yb_off + 2 * yy + 1];
+    const int32_t* __restrict__ k = tables + d.yt_off + (int64_t)yy * d.ky;
+    const uint8_t* __restrict__ p = tmp + d.tmp_off + (int64_t)first * pitch;
+    for (int y = 0; y < count; ++y) {
+        uint32_t v[3];
+        load_quad(p, px0, pitch, v);
+        const int t = k[y];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s[i] += __mul24((int)byte_of(v, i), t);
+        p += pitch;
+    }
+}
+
+// vertical pass of resize A -> uint8 rows of the work buffer (resample_cols_u8 without the statistics)
+__global__ __launch_bounds__(256)
+void geo_cols_u8(const uint8_t* __restrict__ tmp, const GeoDesc* __restrict__ desc, const int32_t* __restrict__ tables,
+                 uint8_t* __restrict__ work) {
+    if (desc[blockIdx.z].n < 2) return;  // block-uniform
+    const GeoResize d = desc[blockIdx.z].r[0];
+    // neighbouring rows share their source rows: one contiguous band of blocks per XCD (gridDim.x is a multiple of 8)
+    const int block = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const int oh = (int)d.dst_h, ow = (int)d.dst_w, pitch = tmp_pitch(ow);
+    const Quad q = quad_of(block, oh, ow);
+    if (!q.active) return;
+    int s[12];
+    geo_cols_quad(tmp, d, tables, q.yy, q.px0, pitch, s);
+    uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+        if (q.px0 + i / 3 < ow) o[i >> 2] |= (uint32_t)clip8(s[i]) << (8 * (i & 3));
+    store_quad(work + d.out_off + (int64_t)q.yy * pitch, q.px0, pitch, o);
+}
+
+// vertical pass of resize B + lookup + zero padding + mask: resample_cols_normalize on the geometry descriptor
+__global__ __launch_bounds__(256)
+void geo_cols_normalize(const uint8_t* __restrict__ tmp, const GeoDesc* __restrict__ desc, const int32_t* __restrict__ tables,
+                        const float* __restrict__ lut, int out_h, int out_w, float* __restrict__ out, uint8_t* __restrict__ mask) {
+    __shared__ float table[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) table[i] = lut[i];
+    __syncthreads();
+    const GeoResize d = desc[blockIdx.z].r[1];
+    int yy = blockIdx.y;  // one contiguous band of rows per XCD, see resample_cols_normalize
+    if (gridDim.x == 1) yy = (yy & 7) * (gridDim.y >> 3) + (yy >> 3);
+    const int px0 = 4 * (blockIdx.x * 256 + threadIdx.x);
+    if (yy >= out_h || px0 >= out_w) return;
+    const int ow = (int)d.dst_w, pitch = tmp_pitch(ow);
+    int s[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool inside = yy < d.dst_h && px0 < ow;
+    if (inside) geo_cols_quad(tmp, d, tables, yy, px0, pitch, s);
+    const int64_t plane = (int64_t)out_h * out_w;
+    float* __restrict__ o = out + (int64_t)blockIdx.z * 3 * plane + (int64_t)yy * out_w + px0;
+    uint8_t* __restrict__ m = mask + (int64_t)blockIdx.z * plane + (int64_t)yy * out_w + px0;
+    float f[3][4];
+    uint32_t pad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const bool real = inside && px0 + i < ow;
+        pad |= real ? 0u : 1u << (8 * i);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c][i] = real ? table[c * 256 + clip8(s[3 * i + c])] : 0.f;
+    }
+    if ((out_w & 3) == 0) {  // rows of the planes are 16-byte aligned
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(o + c * plane) = make_float4(f[c][0], f[c][1], f[c][2], f[c][3]);
+        *reinterpret_cast<uint32_t*>(m) = pad;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (px0 + i < out_w) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[c * plane + i] = f[c][i];
+                m[i] = (uint8_t)(pad >> (8 * i));
+            }
+    }
+}
+
+void launch_geo_rows(hipStream_t s, const uint8_t* blob, const uint8_t* work, const GeoDesc* d, const int32_t* tables, uint8_t* tmp,
+                     int which, int batch, int max_src_h, int max_dst_w, int max_kx) {
+    const dim3 pixels((max_dst_w + 255) / 256, (max_src_h + kRows - 1) / kRows, batch);
+    if (max_kx <= 7)
+        hipLaunchKernelGGL(geo_rows_k<7>, pixels, dim3(256), 0, s, blob, work, d, tables, tmp, which);
+    else if (max_kx <= 9)
+        hipLaunchKernelGGL(geo_rows_k<9>, pixels, dim3(256), 0, s, blob, work, d, tables, tmp, which);
+    else if (max_kx <= 13)
+        hipLaunchKernelGGL(geo_rows_k<13>, pixels, dim3(256), 0, s, blob, work, d, tables, tmp, which);
+    else
+        hipLaunchKernelGGL(geo_rows_any, dim3((max_dst_w * 3 + 255) / 256, max_src_h, batch), dim3(256), 0, s,
+                           blob, work, d, tables, tmp, which);
+}
+
+}  // namespace
+
+extern "C" int grit_image_batch_geo_fwd(const uint8_t* src, const int64_t* geo, const int32_t* tables, uint8_t* tmp, uint8_t* work,
+                                        const float* lut, int batch, int a_src_h, int a_dst_h, int a_dst_w, int a_kx, int b_src_h,
+                                        int b_dst_w, int b_kx, int out_h, int out_w, float* out, uint8_t* mask, void* stream) {
+    if (!src || !geo || !tables || !tmp || !lut || !out || !mask) return GRIT_ERR_BAD_ARG;
+    if (batch <= 0 || b_src_h <= 0 || b_dst_w <= 0 || b_kx <= 0 || out_h <= 0 || out_w <= 0 || b_dst_w > out_w || a_src_h < 0)
+        return GRIT_ERR_BAD_ARG;
+    if (a_src_h > 0 && (!work || a_dst_h <= 0 || a_dst_w <= 0 || a_kx <= 0)) return GRIT_ERR_BAD_ARG;
+    if (((uintptr_t)src | (uintptr_t)tmp | (uintptr_t)work) & 3 || (uintptr_t)geo & 7) return GRIT_ERR_BAD_ARG;
+    if (a_src_h > 65535 || b_src_h > 65535 || out_h > 65535 || batch > 65535 || a_dst_h > 32767 || a_dst_w > 32767)
+        return GRIT_ERR_UNSUPPORTED;
+    const GeoDesc* d = reinterpret_cast<const GeoDesc*>(geo);
+    const hipStream_t s = (hipStream_t)stream;
+    if (a_src_h > 0) {  // some image takes two resizes
+        launch_geo_rows(s, src, work, d, tables, tmp, 0, batch, a_src_h, a_dst_w, a_kx);
+        hipLaunchKernelGGL(geo_cols_u8, dim3((int)GRIT_IMAGE_AUG_BLOCKS(a_dst_h, a_dst_w), 1, batch), dim3(256), 0, s, tmp, d, tables, work);
+    }
+    launch_geo_rows(s, src, work, d, tables, tmp, 1, batch, b_src_h, b_dst_w, b_kx);
+    const int wide = (out_w + 1023) / 1024;
+    hipLaunchKernelGGL(geo_cols_normalize, dim3(wide, wide == 1 ? (out_h + 7) / 8 * 8 : out_h, batch), dim3(256), 0, s,
+                       tmp, d, tables, lut, out_h, out_w, out, mask);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }

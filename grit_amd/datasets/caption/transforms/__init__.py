@@ -4,14 +4,16 @@ train / valid transforms = resize policy only: ToTensor and Normalize are applie
 resampling and the batch padding (`collate_images`), so a transform returns a `Deferred` image, not a tensor.
 RandAugment: `cfg.randaug = 'device'` makes the train transform draw the reference's four random operations per image
 (transforms/randaug.py) and the device apply them between the resize and ToTensor, bit-identically to Pillow.  The
-reference's `randaug: True` (PIL in the dataset worker) is not provided and raises."""
-from grit_amd.ops.image_batch import MEAN, STD, image_batch
+reference's `randaug: True` (PIL in the dataset worker) is not provided and raises.
+`resize_name = 'normal'` is torchvision's Resize((h, w)) = PIL BILINEAR: a `FixedResize` whose records ask for bilinear taps, which
+`collate_images` resamples through the plan path of the device pipeline (image_batch_geo); it has no augmented variant."""
+from grit_amd.ops.image_batch import MEAN, STD, image_batch, image_batch_geo
 from grit_amd.utils.misc import NestedTensor
 
 from .randaug import RandAugment, augment_list
 from .utils import Deferred, FixedResize, MaxWHResize, MinMaxResize
 
-RESIZE = {'minmax': MinMaxResize, 'maxwh': MaxWHResize}
+RESIZE = {'minmax': MinMaxResize, 'maxwh': MaxWHResize, 'normal': FixedResize}  # 'normal': torchvision Resize = PIL BILINEAR
 
 
 class Sequence(object):
@@ -31,10 +33,8 @@ def get_transform(cfg):
     if randaug and randaug != 'device':
         raise NotImplementedError("randaug=True is the reference's host-side PIL augmentation, which this build does not run; "
                                   "set transform_cfg.randaug = 'device' for the same operations on the GPU")
-    if cfg.resize_name == 'normal':
-        # the reference's 'normal' policy is torchvision Resize = PIL BILINEAR; the device resampler implements Pillow's
-        # BICUBIC taps only, and silently resampling with another filter would change the input pixels
-        raise NotImplementedError("resize_name='normal' (bilinear torchvision Resize) is not provided; use 'maxwh' or 'minmax'")
+    if randaug == 'device' and cfg.resize_name == 'normal':
+        raise NotImplementedError("randaug='device' follows a bicubic resize ('maxwh', 'minmax'); the bilinear 'normal' policy has no augmented path")
     resize = RESIZE[cfg.resize_name](cfg.size)
     if randaug == 'device':
         return {'train': Sequence([resize, RandAugment()]), 'valid': resize}
@@ -50,6 +50,14 @@ def collate_images(items, device=None, pad_to=None):
     sizes = [it.size for it in items]
     plans = [it.augment for it in items]
     augment = None if all(p is None for p in plans) else [p or () for p in plans]
-    tensors, mask = image_batch([it.pixels for it in items], sizes, MEAN, STD, device, pad_to, augment=augment)
+    filters = set(it.filter for it in items)
+    if filters == {'bilinear'}:  # the bilinear taps run on the plan path: one resize per image
+        if augment is not None:
+            raise NotImplementedError("RandAugment after a bilinear resize is not provided: the augmented path resamples with bicubic taps")
+        tensors, mask = image_batch_geo([it.pixels for it in items], [(('resize',) + tuple(s),) for s in sizes], MEAN, STD, device, pad_to)
+    elif filters == {'bicubic'}:
+        tensors, mask = image_batch([it.pixels for it in items], sizes, MEAN, STD, device, pad_to, augment=augment)
+    else:
+        raise ValueError("the images of a batch share one resampling filter, got %s" % sorted(filters))
     padded = len(set(sizes)) > 1 or (pad_to is not None and tuple(pad_to) != tuple(sizes[0]))
     return NestedTensor(tensors, mask, any_padding=padded)

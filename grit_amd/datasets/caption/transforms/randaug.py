@@ -51,4 +51,4 @@ class RandAugment(object):
             raise TypeError("RandAugment follows the resize policy: it expects the Deferred image a policy returns")
         if x.augment is not None:
             raise ValueError("image already carries an augmentation plan")
-        return Deferred(x.pixels, x.size, self.draw())
+        return Deferred(x.pixels, x.size, self.draw(), x.filter)

@@ -8,11 +8,12 @@ import numpy as np
 
 class Deferred(object):
     """A decoded RGB image ([h, w, 3] uint8) waiting for the device-side resize to `size` = (newh, neww) and, when
-    `augment` is a plan of transforms/randaug.py, for the augmentation that follows the resize."""
-    __slots__ = ('pixels', 'size', 'augment')
+    `augment` is a plan of transforms/randaug.py, for the augmentation that follows the resize.  `filter` is Pillow's
+    resampling filter of that resize, 'bicubic' or 'bilinear'."""
+    __slots__ = ('pixels', 'size', 'augment', 'filter')
 
-    def __init__(self, pixels, size, augment=None):
-        self.pixels, self.size, self.augment = pixels, size, augment
+    def __init__(self, pixels, size, augment=None, filter='bicubic'):
+        self.pixels, self.size, self.augment, self.filter = pixels, size, augment, filter
 
 
 def _pixels(x):
@@ -24,10 +25,11 @@ def _pixels(x):
 
 
 class _Policy(object):
+    filter = 'bicubic'
 
     def __call__(self, x):
         pixels = _pixels(x)
-        return Deferred(pixels, self.output_size(int(pixels.shape[0]), int(pixels.shape[1])))
+        return Deferred(pixels, self.output_size(int(pixels.shape[0]), int(pixels.shape[1])), filter=self.filter)
 
 
 class MaxWHResize(_Policy):
@@ -61,10 +63,13 @@ class MinMaxResize(_Policy):
 
 
 class FixedResize(_Policy):
-    """torchvision.transforms.Resize((h, w)) of the 'normal' entry: always the configured size."""
+    """torchvision.transforms.Resize((h, w)) of the 'normal' entry: always the configured size, PIL's BILINEAR."""
+    filter = 'bilinear'
 
     def __init__(self, size):
-        self.size = tuple(size)
+        if not isinstance(size, (list, tuple)) or len(size) != 2:
+            raise ValueError("resize_name='normal' needs size as an (h, w) pair, got %r" % (size,))
+        self.size = (int(size[0]), int(size[1]))
 
     def output_size(self, h, w):
         return self.size

@@ -16,7 +16,12 @@ With `augment` (one plan per image, drawn by datasets/caption/transforms/randaug
 the reference's RandAugment operations before the float stage (grit_image_batch_aug_fwd: one launch per stage for the
 whole batch, every image with its own operation).  The host turns a plan into integers only -- operation codes, the bits
 of the fp32 factors, Pillow's 16.16 fixed-point affine coefficients, the index tables of the translations (`plan_augment`)
--- which travel in the same pinned blob; the result is bit-identical to Pillow's."""
+-- which travel in the same pinned blob; the result is bit-identical to Pillow's.
+
+`image_batch_geo` is the detector's input (datasets/detection/transforms.py): per image a plan of ('hflip',), ('resize', oh, ow)
+and ('crop', top, left, h, w) steps, resized with Pillow's BILINEAR taps as torchvision's `resize` does.  `plan_geo` folds a
+plan into at most two resizes over source windows -- a crop moves the window, a flip mirrors the taps of the next horizontal
+pass -- and grit_image_batch_geo_fwd runs them: two launches per batch, four when some image resizes twice."""
 import ctypes
 import functools
 import math
@@ -40,19 +45,34 @@ def tmp_pitch(dst_w):
 
 
 @functools.lru_cache(maxsize=4096)
-def axis_taps(in_size, out_size):
-    """-> (ksize, bounds int32 [out_size, 2], taps int32 [out_size, ksize]) of one axis (host, cached)."""
+def axis_taps(in_size, out_size, filter='bicubic'):
+    """-> (ksize, bounds int32 [out_size, 2], taps int32 [out_size, ksize]) of one axis (host, cached); filter: Pillow's
+    'bicubic' or 'bilinear'."""
     lib = _lib.load()
-    ksize = lib.grit_resample_taps_bicubic(in_size, out_size, None, None, 0)
+    if filter not in ('bicubic', 'bilinear'):
+        raise ValueError("unknown resampling filter %r" % (filter,))
+    name = "grit_resample_taps_" + filter
+    build = getattr(lib, name)
+    ksize = build(in_size, out_size, None, None, 0)
     if ksize <= 0:
-        raise _lib.GritHipError("grit_resample_taps_bicubic(%d, %d) failed" % (in_size, out_size))
+        raise _lib.GritHipError("%s(%d, %d) failed" % (name, in_size, out_size))
     bounds = np.empty((out_size, 2), np.int32)
     taps = np.empty((out_size, ksize), np.int32)
-    got = lib.grit_resample_taps_bicubic(in_size, out_size, bounds.ctypes.data_as(ctypes.c_void_p),
-                                         taps.ctypes.data_as(ctypes.c_void_p), taps.size)
+    got = build(in_size, out_size, bounds.ctypes.data_as(ctypes.c_void_p), taps.ctypes.data_as(ctypes.c_void_p), taps.size)
     if got != ksize:
-        raise _lib.GritHipError("grit_resample_taps_bicubic(%d, %d) failed" % (in_size, out_size))
+        raise _lib.GritHipError("%s(%d, %d) failed" % (name, in_size, out_size))
     return ksize, bounds, taps
+
+
+@functools.lru_cache(maxsize=4096)
+def mirrored_taps(in_size, out_size, filter='bilinear'):
+    """axis_taps for a row that is read back to front: resize(hflip(row)) = these taps on the row as stored.  Each output's
+    taps are reversed and first' = in_size - first - count; integer sums, so the order of the terms does not matter."""
+    ksize, bounds, taps = axis_taps(in_size, out_size, filter)
+    first, count = bounds[:, 0], bounds[:, 1]
+    source = count[:, None] - 1 - np.arange(ksize, dtype=np.int32)[None, :]
+    flipped = np.where(source >= 0, np.take_along_axis(taps, np.maximum(source, 0), 1), 0).astype(np.int32)
+    return ksize, np.stack([in_size - first - count, count], 1).astype(np.int32), flipped
 
 
 @functools.lru_cache(maxsize=16)
@@ -220,6 +240,38 @@ def plan_augment(sizes, plans, table_base=0):
     return aug, extra, n_stages, off
 
 
+def _upload_pixels(imgs, offsets, src_bytes, device):
+    """The packed source blob on the device, GRIT_IMAGE_SRC_PAD readable bytes behind the last image."""
+    if all(im.is_cuda for im in imgs):
+        return torch.cat([im.reshape(-1) for im in imgs] + [torch.zeros(SRC_PAD, dtype=torch.uint8, device=device)])
+    if all(im.is_cuda or im.is_pinned() for im in imgs):  # decoder wrote into pinned memory: no staging copy
+        src = torch.empty(src_bytes + SRC_PAD, dtype=torch.uint8, device=device)
+        for im, off in zip(imgs, offsets):
+            src[off:off + im.numel()].copy_(im.reshape(-1), non_blocking=True)
+        return src
+    slot = _pixels_staging.take(src_bytes + SRC_PAD)  # one pinned staging blob, one asynchronous upload
+    for im, off in zip(imgs, offsets):
+        slot[0][off:off + im.numel()].copy_(im.reshape(-1))
+    return _pixels_staging.upload(slot, src_bytes + SRC_PAD, device)
+
+
+def _upload_tables(device, *arrays):
+    """Descriptor (int64) and tables (int32) travel in one pinned blob: -> one device view per array (None stays None)."""
+    sizes = [0 if a is None else a.dtype.itemsize * a.size for a in arrays]
+    slot = _tables_staging.take(sum(sizes))
+    at = 0
+    for a, n in zip(arrays, sizes):
+        if n:
+            slot[0][at:at + n].copy_(torch.from_numpy(a.reshape(-1)).view(torch.uint8))
+        at += n
+    dev = _tables_staging.upload(slot, at, device)
+    views, at = [], 0
+    for n in sizes:
+        views.append(dev[at:at + n])
+        at += n
+    return views
+
+
 def image_batch(images, sizes, mean=MEAN, std=STD, device=None, pad_to=None, augment=None):
     """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device); sizes: list of (oh, ow).
     augment: None, or one RandAugment plan ((name, magnitude, negate), ...) per image (may be empty), applied to the
@@ -251,27 +303,8 @@ def image_batch(images, sizes, mean=MEAN, std=STD, device=None, pad_to=None, aug
         H, W = int(pad_to[0]), int(pad_to[1])
     B = len(imgs)
     with _lib.device_guard(device):
-        if all(im.is_cuda for im in imgs):
-            src = torch.cat([im.reshape(-1) for im in imgs] + [torch.zeros(SRC_PAD, dtype=torch.uint8, device=device)])
-        elif all(im.is_cuda or im.is_pinned() for im in imgs):  # decoder wrote into pinned memory: no staging copy
-            src = torch.empty(src_bytes + SRC_PAD, dtype=torch.uint8, device=device)
-            for im, off in zip(imgs, desc[:, 0].tolist()):
-                src[off:off + im.numel()].copy_(im.reshape(-1), non_blocking=True)
-        else:  # one pinned staging blob, one asynchronous upload
-            slot = _pixels_staging.take(src_bytes + SRC_PAD)
-            for im, off in zip(imgs, desc[:, 0].tolist()):
-                slot[0][off:off + im.numel()].copy_(im.reshape(-1))
-            src = _pixels_staging.upload(slot, src_bytes + SRC_PAD, device)
-        # descriptor (int64) and tables (int32) travel in one pinned blob
-        nd, nt = 8 * desc.size, 4 * tables.size
-        na = 4 * aug.size if augment is not None else 0
-        slot = _tables_staging.take(nd + nt + na)
-        slot[0][:nd].copy_(torch.from_numpy(desc.reshape(-1)).view(torch.uint8))
-        slot[0][nd:nd + nt].copy_(torch.from_numpy(tables).view(torch.uint8))
-        if na:
-            slot[0][nd + nt:nd + nt + na].copy_(torch.from_numpy(aug.reshape(-1)).view(torch.uint8))
-        dev = _tables_staging.upload(slot, nd + nt + na, device)
-        d_desc, d_tables, d_aug = dev[:nd], dev[nd:nd + nt], dev[nd + nt:]
+        src = _upload_pixels(imgs, desc[:, 0].tolist(), src_bytes, device)
+        d_desc, d_tables, d_aug = _upload_tables(device, desc, tables, aug if augment is not None else None)
         tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=device)
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
         mask = torch.empty(B, H, W, dtype=torch.bool, device=device)
@@ -289,4 +322,136 @@ def image_batch(images, sizes, mean=MEAN, std=STD, device=None, pad_to=None, aug
         st = lib.grit_image_batch_fwd(p(src), p(d_desc), p(d_tables), p(tmp), p(_lut(tuple(mean), tuple(std), device)),
                                       B, int(desc[:, 1].max()), max_dst_w, int(desc[:, 5].max()), H, W, p(out), p(mask), _lib.current_stream_ptr())
         _lib.check(st, "grit_image_batch_fwd")
+    return out, mask
+
+
+GEO_FIELDS = _lib.IMAGE_GEO_FIELDS
+
+
+def fold_geo(h, w, ops):
+    """One image's plan -> its resizes, each (top, left, win_h, win_w, mirrored, oh, ow): the window of the image that resize
+    reads (the [h, w] source for the first, the previous result for the second) and whether its rows are read back to front.
+    A crop moves the window (inside a pending flip its left edge is counted from the right), a flip toggles `mirrored` of the
+    next resize; a flip or crop with no resize after it, or an empty plan, gets an identity resize."""
+    resizes = []
+    top, left, ch, cw, mirrored = 0, 0, h, w, False
+    full = (h, w)  # size of the image the window lies in
+    for op in ops:
+        if op[0] == 'hflip' and len(op) == 1:
+            mirrored = not mirrored
+        elif op[0] == 'crop' and len(op) == 5:
+            t, l, hh, ww = (int(v) for v in op[1:])
+            if t < 0 or l < 0 or hh <= 0 or ww <= 0 or t + hh > ch or l + ww > cw:
+                raise ValueError("crop (top %d, left %d, %d x %d) leaves the %d x %d image" % (t, l, hh, ww, ch, cw))
+            top += t
+            left += cw - l - ww if mirrored else l
+            ch, cw = hh, ww
+        elif op[0] == 'resize' and len(op) == 3:
+            oh, ow = int(op[1]), int(op[2])
+            if oh <= 0 or ow <= 0:
+                raise ValueError("empty target size: %s" % (op,))
+            resizes.append((top, left, ch, cw, mirrored, oh, ow))
+            top, left, ch, cw, mirrored, full = 0, 0, oh, ow, False, (oh, ow)
+        else:
+            raise ValueError("unknown plan step %r" % (op,))
+    if not resizes or mirrored or (top, left, ch, cw) != (0, 0) + full:
+        resizes.append((top, left, ch, cw, mirrored, ch, cw))
+    if len(resizes) > 2:
+        raise ValueError("a plan folds into at most two resizes, this one needs %d: %s" % (len(resizes), tuple(ops)))
+    return resizes
+
+
+class GeoPlan(object):
+    """Host side of one detector batch, see plan_geo."""
+    __slots__ = ('geo', 'tables', 'tmp_bytes', 'work_bytes', 'src_bytes', 'src_offsets', 'sizes', 'a_max', 'b_max')
+
+
+def plan_geo(shapes, plans, filter='bilinear'):
+    """shapes [(h, w)], one plan per image -> GeoPlan: geo int64 [B, 30] (grit_hip.h), tables int32 [n], the bytes of the
+    intermediate, of the work buffer (without its readable tail) and of the source blob, every image's offset in the blob,
+    the final (oh, ow) per image, and the maxima (src_h, dst_h, dst_w, kx) over the A and the B records (A: zeros when no
+    image resizes twice)."""
+    p = GeoPlan()
+    p.geo = np.zeros((len(shapes), GEO_FIELDS), np.int64)
+    parts, n, placed = [], 0, {}
+    p.src_offsets, p.sizes = [], []
+    src_off = tmp_off = work_off = 0
+    a_max, b_max = [0, 0, 0, 0], [0, 0, 0, 0]
+
+    def place(key, arr):
+        nonlocal n
+        if key not in placed:
+            placed[key] = n
+            parts.append(arr.reshape(-1))
+            n += arr.size
+            if n % 2:  # the kernels read (first, count) pairs as one 8-byte load
+                parts.append(np.zeros(1, np.int32))
+                n += 1
+        return placed[key]
+
+    for i, ((h, w), ops) in enumerate(zip(shapes, plans)):
+        if min(h, w) <= 0:
+            raise ValueError("empty image: %s" % ((h, w),))
+        resizes = fold_geo(int(h), int(w), ops)
+        p.geo[i, 0] = len(resizes)
+        buf, base, pitch = 0, src_off, 3 * w  # where the first resize reads
+        for which, (top, left, wh, ww, mirrored, oh, ow) in enumerate(resizes, 2 - len(resizes)):  # a single resize is record B
+            kx, xb, xt = (mirrored_taps if mirrored else axis_taps)(ww, ow, filter)
+            ky, yb, yt = axis_taps(wh, oh, filter)
+            out_off = work_off if which == 0 else 0
+            p.geo[i, 2 + 14 * which:16 + 14 * which] = (
+                buf, base + top * pitch + 3 * left, pitch, wh, oh, ow, kx, ky,
+                place(('b', ww, ow, mirrored), xb), place(('t', ww, ow, mirrored), xt),
+                place(('b', wh, oh, False), yb), place(('t', wh, oh, False), yt), tmp_off, out_off)
+            tmp_off += wh * tmp_pitch(ow)
+            m = a_max if which == 0 else b_max
+            m[:] = max(m[0], wh), max(m[1], oh), max(m[2], ow), max(m[3], kx)
+            if which == 0:  # the second resize reads this one's rows in the work buffer
+                buf, base, pitch = 1, work_off, tmp_pitch(ow)
+                work_off += oh * tmp_pitch(ow)
+        p.src_offsets.append(src_off)
+        p.sizes.append((oh, ow))
+        src_off += h * w * 3
+    if max(src_off, tmp_off, work_off) >= 2 ** 31:
+        raise ValueError("batch exceeds 2 GiB")
+    p.tables = np.concatenate(parts)
+    p.tmp_bytes, p.work_bytes, p.src_bytes, p.a_max, p.b_max = tmp_off, work_off, src_off, tuple(a_max), tuple(b_max)
+    return p
+
+
+def image_batch_geo(images, plans, mean=MEAN, std=STD, device=None, pad_to=None):
+    """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device); plans: per image a sequence of ('hflip',),
+    ('resize', oh, ow) and ('crop', top, left, h, w) in the order a PIL chain would apply them (at most two resizes; resizes
+    are Pillow's BILINEAR, what torchvision.transforms.functional.resize does to a PIL image).
+
+    -> (tensors [B, 3, H, W] f32, mask [B, H, W] bool) on `device` as image_batch returns them."""
+    imgs = [_as_u8(im) for im in images]
+    if len(imgs) == 0 or len(imgs) != len(plans):
+        raise ValueError("need one plan per image and at least one image")
+    if device is None:
+        device = imgs[0].device if imgs[0].is_cuda else torch.device('cuda', torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.GritHipError("Not implemented on the CPU: the image pipeline runs as HIP kernels")
+    lib = _lib.load()
+    g = plan_geo([tuple(im.shape[:2]) for im in imgs], plans)
+    H, W = max(s[0] for s in g.sizes), max(s[1] for s in g.sizes)
+    if pad_to is not None:
+        if pad_to[0] < H or pad_to[1] < W:
+            raise ValueError("pad_to %s is smaller than the largest resized image (%d, %d)" % (tuple(pad_to), H, W))
+        H, W = int(pad_to[0]), int(pad_to[1])
+    B = len(imgs)
+    with _lib.device_guard(device):
+        src = _upload_pixels(imgs, g.src_offsets, g.src_bytes, device)
+        d_geo, d_tables = _upload_tables(device, g.geo, g.tables)
+        tmp = torch.empty(g.tmp_bytes, dtype=torch.uint8, device=device)
+        # the row pass of resize B fetches whole dwords past a window that ends with the buffer: the blob's readable tail
+        work = torch.empty(g.work_bytes + SRC_PAD, dtype=torch.uint8, device=device) if g.work_bytes else None
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=device)
+        mask = torch.empty(B, H, W, dtype=torch.bool, device=device)
+        p = _lib.ptr
+        st = lib.grit_image_batch_geo_fwd(p(src), p(d_geo), p(d_tables), p(tmp), p(work), p(_lut(tuple(mean), tuple(std), device)), B,
+                                          g.a_max[0], g.a_max[1], g.a_max[2], g.a_max[3], g.b_max[0], g.b_max[2], g.b_max[3],
+                                          H, W, p(out), p(mask), _lib.current_stream_ptr())
+        _lib.check(st, "grit_image_batch_geo_fwd")
     return out, mask

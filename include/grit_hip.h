@@ -37,6 +37,9 @@
  *                           nested_tensor_from_tensor_list (engine/utils.py:278-295)
  *   grit_image_batch_aug_fwd <- the same with RandAugment between the resize and ToTensor
  *                           (datasets/caption/transforms/randaug.py:11-104: PIL transform / rotate / ImageOps / ImageEnhance)
+ *   grit_resample_taps_bilinear, grit_image_batch_geo_fwd
+ *                        <- the detector's input: hflip / resize / crop on PIL images (datasets/detection/transforms.py:107-223,
+ *                           torchvision's resize = Image.resize(BILINEAR)), then ToTensor, Normalize, padding and mask
  *   grit_gemm_bf16_nt    <- nn.Linear + nn.GELU of Mlp (models/common/swin_model.py:31-37) and their autograd backward:
  *                           fc1 + bias + exact GELU in one pass; fc2's input gradient x GELU' + fc1's bias gradient in one pass
  *   grit_topk_rows_f32   <- Transformer.select (models/caption/transformer.py:184-188): sort of beam x vocabulary candidates
@@ -66,7 +69,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 51
+#define GRIT_ABI_VERSION 52
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -546,7 +549,8 @@ int grit_adamw_flat_dev(float* param, const void* grad, int grad_is_bf16, float*
  * (bit-identical to Image.resize(size, Image.BICUBIC) on an RGB image), x/255, (x - mean)/std, zero padding to the
  * batch maximum and the padding mask -- transforms/utils.py:4-45, transforms/__init__.py:6-32, engine/utils.py:278-295.
  *
- * grit_resample_taps_bicubic (host code, no GPU work): the tap table of one axis.
+ * grit_resample_taps_bicubic, grit_resample_taps_bilinear (host code, no GPU work): the tap table of one axis for Pillow's
+ * BICUBIC / BILINEAR filter.
  *   bounds [out_size][2] = (first source index, tap count);  taps [out_size][ksize] 22-bit fixed point, zero past the count
  *   returns ksize (> 0); with bounds == taps == NULL only ksize is computed; -GRIT_ERR_BAD_ARG on bad sizes / capacity
  *
@@ -566,6 +570,7 @@ int grit_adamw_flat_dev(float* param, const void* grad, int grad_is_bf16, float*
 #define GRIT_IMAGE_SRC_PAD 64
 #define GRIT_IMAGE_TMP_PITCH(dst_w) ((3 * (dst_w) + 3) & ~3)
 int grit_resample_taps_bicubic(int in_size, int out_size, int32_t* bounds, int32_t* taps, long taps_capacity);
+int grit_resample_taps_bilinear(int in_size, int out_size, int32_t* bounds, int32_t* taps, long taps_capacity);
 int grit_image_batch_fwd(const uint8_t* src, const int64_t* desc, const int32_t* tables, uint8_t* tmp, const float* lut,
                          int batch, int max_src_h, int max_dst_w, int max_kx, int out_h, int out_w, float* out,
                          uint8_t* mask, void* stream);
@@ -619,6 +624,37 @@ int grit_image_batch_aug_fwd(const uint8_t* src, const int64_t* desc, const int3
                              const int32_t* aug, int n_stages, uint8_t* work, long work_bytes, uint32_t* stats, int batch,
                              int max_src_h, int max_dst_h, int max_dst_w, int max_kx, int out_h, int out_w, float* out,
                              uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The detector's input pipeline (datasets/detection/transforms.py: hflip, resize, crop chained on PIL images, then ToTensor,
+ * Normalize and nested_tensor_from_tensor_list): per image one or two resizes, A then B, each over a source window.  The host
+ * folds a crop into the window (first byte, height; the width is the in_size of the x table) and a horizontal flip into the x
+ * table of the next resize (taps reversed, first' = w - first - count), so the kernels see neither.  Any tap tables may be
+ * used; with grit_resample_taps_bilinear the result is bit-identical to the PIL chain.
+ *
+ * grit_image_batch_geo_fwd (rows B, columns B + lookup + padding + mask; before them rows A, columns A -> uint8 work buffer
+ * when a_src_h > 0; images with one resize return at once from the first two):
+ *   src     the uint8 blob of grit_image_batch_fwd (4-byte aligned, GRIT_IMAGE_SRC_PAD readable bytes past the last image)
+ *   geo     [batch][GRIT_IMAGE_GEO_FIELDS] int64 (device): n = number of resizes (1 or 2), one spare, then two records of 14,
+ *           A and B (A all zero when n = 1; B is always the resize that ends in `out`):
+ *             buf      0: the window lies in src, 1: in work (B of a two-resize image)
+ *             off      byte offset of the window's first pixel in that buffer (>= 0, any alignment)
+ *             pitch    bytes between source rows: 3 * width of the stored image, or GRIT_IMAGE_TMP_PITCH(A's dst_w)
+ *             src_h    rows of the window;  dst_h, dst_w  the resized size
+ *             kx, ky, xb_off, xt_off, yb_off, yt_off   as in grit_image_batch_fwd's descriptor (tables over the window's size)
+ *             tmp_off  byte offset (multiple of 4) of this resize's slot in tmp: src_h rows of GRIT_IMAGE_TMP_PITCH(dst_w)
+ *             out_off  A: byte offset (multiple of 4) of its result in work, dst_h rows of GRIT_IMAGE_TMP_PITCH(dst_w);  B: zero
+ *   tmp     uint8 scratch, 4-byte aligned, holding every slot (A's and B's slots of one image must not overlap)
+ *   work    uint8 scratch, 4-byte aligned: every A result plus GRIT_IMAGE_SRC_PAD readable bytes; may be NULL when a_src_h = 0
+ *   a_src_h, a_dst_h, a_dst_w, a_kx   maxima of src_h, dst_h, dst_w, kx over the A records; a_src_h = 0: no image has two resizes
+ *   b_src_h, b_dst_w, b_kx            the same over the B records;  b_dst_w <= out_w, every B dst_h <= out_h
+ *   lut, out, mask, out_h, out_w      as for grit_image_batch_fwd
+ * No atomics, nothing to zero; grid extents <= 65535, A's dst_h, dst_w <= 32767.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_IMAGE_GEO_FIELDS 30
+int grit_image_batch_geo_fwd(const uint8_t* src, const int64_t* geo, const int32_t* tables, uint8_t* tmp, uint8_t* work,
+                             const float* lut, int batch, int a_src_h, int a_dst_h, int a_dst_w, int a_kx, int b_src_h,
+                             int b_dst_w, int b_kx, int out_h, int out_w, float* out, uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * bf16 MFMA GEMM with fused epilogues (Swin Mlp, models/common/swin_model.py:31-37, on the [B*H*W, C] token maps).

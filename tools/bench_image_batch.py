@@ -2,7 +2,12 @@
 640x640 batch.  `python tools/bench_image_batch.py [--batch 32] [--iters 50]`
 
 `--augment`: the RandAugment path instead -- batch of 480 x 640 sources -> (384, 512), `image_batch` with and without
-plans (drawn once with a fixed seed), same process, alternating rounds, HIP-event time per batch, launches and bytes."""
+plans (drawn once with a fixed seed), same process, alternating rounds, HIP-event time per batch, launches and bytes.
+
+`--detector`: the detector's input pipeline -- batch of 500 x 375 sources, plans drawn once under a fixed seed from
+make_transforms('train', 'train'), `image_batch_geo` next to the plain bicubic `image_batch` to the same target sizes, device-resident
+input, alternating rounds in one process, HIP-event time per batch; where Pillow is importable also the host chain (flip, resize,
+crop, resize; one core) per batch."""
 import argparse
 import json
 import os
@@ -15,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from grit_amd.datasets.caption.transforms import MaxWHResize, RandAugment  # noqa: E402
-from grit_amd.ops.image_batch import image_batch, plan_augment, tmp_pitch  # noqa: E402
+from grit_amd.ops.image_batch import image_batch, image_batch_geo, plan_augment, plan_geo, tmp_pitch  # noqa: E402
 
 
 def timed(fn, iters):
@@ -61,15 +66,73 @@ def augmented(a):
                               'GB_per_s': round(nbytes / best[k][0] / 1e6, 1)}))
 
 
+def pillow_chain_ms(host, plans):
+    """The same plans as a PIL chain on this core, milliseconds per batch; None without Pillow."""
+    try:
+        from PIL import Image
+    except ImportError:
+        return None
+    pil = [Image.fromarray(h.numpy(), 'RGB') for h in host]
+    t0 = time.perf_counter()
+    for im, plan in zip(pil, plans):
+        for op in plan:
+            if op[0] == 'hflip':
+                im = im.transpose(Image.FLIP_LEFT_RIGHT)
+            elif op[0] == 'crop':
+                im = im.crop((op[2], op[1], op[2] + op[4], op[1] + op[3]))
+            else:
+                im = im.resize((op[2], op[1]), Image.BILINEAR)
+        im.load()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def detector(a):
+    from grit_amd.datasets.detection import make_transforms
+    rng = np.random.default_rng(0)
+    host = [torch.from_numpy(rng.integers(0, 256, (375, 500, 3), dtype=np.uint8)) for _ in range(a.batch)]
+    dev = [h.cuda() for h in host]
+    random.seed(0)
+    torch.manual_seed(0)
+    recipe = make_transforms('train', 'train')
+    plans = [recipe(h.numpy(), {})[0].plan for h in host]
+    g = plan_geo([(375, 500)] * a.batch, plans)
+    H, W = max(s[0] for s in g.sizes), max(s[1] for s in g.sizes)
+    two = int((g.geo[:, 0] == 2).sum())
+    src = a.batch * 375 * 500 * 3
+    geo_bytes = src + 2 * g.tmp_bytes + 2 * g.work_bytes + a.batch * H * W * 13  # a two-resize image reads the source once, the work buffer once
+    runs = {'bicubic image_batch': lambda: image_batch(dev, g.sizes, device='cuda'),
+            'detector image_batch_geo': lambda: image_batch_geo(dev, plans, device='cuda')}
+    for fn in runs.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    best = {k: (float('inf'), float('inf')) for k in runs}
+    for _ in range(a.rounds):  # alternate, keep the fastest round of each
+        for k, fn in runs.items():
+            best[k] = min(best[k], timed(fn, a.iters))
+    for k in runs:
+        line = {'case': '500x375 train recipe, ' + k, 'input': 'device-resident', 'batch': a.batch, 'out': [H, W], 'two_resize_images': two,
+                'ms_per_batch': round(best[k][0], 3), 'wall_ms_per_batch': round(best[k][1], 3)}
+        if 'geo' in k:
+            line.update(launches=4 if two else 2, moved_MB=round(geo_bytes / 1e6, 1), GB_per_s=round(geo_bytes / best[k][0] / 1e6, 1))
+        print(json.dumps(line))
+    ms = pillow_chain_ms(host, plans)
+    print(json.dumps({'case': '500x375 train recipe, Pillow chain on one host core (no ToTensor / Normalize / padding)', 'batch': a.batch,
+                      'ms_per_batch': None if ms is None else round(ms, 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--iters', type=int, default=50)
     ap.add_argument('--augment', action='store_true', help="time the RandAugment path next to the plain one")
-    ap.add_argument('--rounds', type=int, default=5, help="alternating rounds of --iters batches each (--augment)")
+    ap.add_argument('--detector', action='store_true', help="time the detector's input pipeline next to the plain bicubic one")
+    ap.add_argument('--rounds', type=int, default=5, help="alternating rounds of --iters batches each (--augment, --detector)")
     a = ap.parse_args()
     if a.augment:
         return augmented(a)
+    if a.detector:
+        return detector(a)
     rng = np.random.default_rng(0)
     coco = [(480, 640), (427, 640), (640, 480), (333, 500), (375, 500), (500, 375), (640, 428), (480, 640)]
     for name, shapes, policy in (('coco->maxwh(384,640)', [coco[i % 8] for i in range(a.batch)], MaxWHResize((384, 640))),

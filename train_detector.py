@@ -1,15 +1,19 @@
 """Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
 
-    python train_detector.py --synthetic --steps 3 [--batch-size 2] [--size 224] [--bf16] [key=value ...]
+    python train_detector.py --synthetic [--augment] --steps 3 [--batch-size 2] [--size 224] [--bf16] [key=value ...]
 
 The Visual Genome / LMDB readers, the hook-based solver and the COCO-style evaluation are out of scope of this build, so the only
 data source here is `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
 (grit_amd/models/detection/od_losses.py) and engine.det_engine.train_step, and prints the loss dictionary of every step.
+`--augment` feeds the input pipeline of the recipe instead of noise tensors: seeded uint8 images of mixed sizes with pixel boxes go
+through datasets.detection.make_transforms('train', 'train') -- flip, random resize, ratio resize + crop + resize -- and
+collate_detection, which resamples the batch on the device (`--size` does not apply: the recipe decides the sizes).
 `--bf16` trains on the path the captioner uses (grit_amd.amp.Bf16Compute: bf16 compute copies, fp32 masters, flat AdamW and gradient
 clipping on the device, the reference's four parameter groups and MultiStepLR; engine.det_engine.build_optimizers_schedulers).
 Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
 """
 import argparse
+import random
 
 import torch
 
@@ -33,9 +37,35 @@ def synthetic_batch(generator, batch_size, size, num_classes, max_targets, devic
     return NestedTensor(images.to(device), mask.to(device), any_padding=False), targets
 
 
+SOURCE_SIZES = ((500, 375), (375, 500), (500, 333), (640, 480), (480, 640), (400, 300))  # (w, h) of the synthetic "photos"
+
+
+def augmented_batch(generator, batch_size, num_classes, max_targets, device, transform):
+    """Per image: uint8 noise of one of SOURCE_SIZES and 1..max_targets boxes in pixels (xyxy) -> `transform` (which draws from the
+    global `random` and torch generators and finishes the targets on the host) -> collate_detection.  An image whose crop removed
+    every box is drawn again; no pixel has been touched by then."""
+    from grit_amd.datasets.detection import collate_detection
+    items = []
+    while len(items) < batch_size:
+        w, h = SOURCE_SIZES[int(torch.randint(0, len(SOURCE_SIZES), (1,), generator=generator))]
+        image = torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=generator)
+        n = int(torch.randint(1, max_targets + 1, (1,), generator=generator))
+        extent = torch.tensor([w, h], dtype=torch.float32)
+        wh = (0.05 + 0.4 * torch.rand(n, 2, generator=generator)) * extent
+        corner = (extent - wh) * torch.rand(n, 2, generator=generator)
+        target = {'boxes': torch.cat([corner, corner + wh], 1), 'labels': torch.randint(0, num_classes, (n,), generator=generator),
+                  'area': wh.prod(1), 'iscrowd': torch.zeros(n, dtype=torch.int64), 'size': torch.tensor([h, w]),
+                  'orig_size': torch.tensor([h, w])}
+        record, target = transform(image.numpy(), target)
+        if len(target['labels']):
+            items.append((record, target))
+    return collate_detection(items, device=device)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--synthetic', action='store_true', help='seeded random images and targets (the only data source of this build)')
+    ap.add_argument('--augment', action='store_true', help="with --synthetic: uint8 images through the recipe's transforms and the device collator")
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--batch-size', type=int, default=None)
     ap.add_argument('--size', type=int, default=224, help='image side')
@@ -72,8 +102,15 @@ def main():
         optimizer = _plain_optimizer(model, config)
     g = torch.Generator().manual_seed(config.exp.seed)
     batch_size = args.batch_size or config.optimizer.batch_size
+    if args.augment:
+        from grit_amd.datasets.detection import make_transforms
+        random.seed(config.exp.seed)
+        transform = make_transforms('train', 'train')
     for step in range(args.steps):
-        samples, targets = synthetic_batch(g, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
+        if args.augment:
+            samples, targets = augmented_batch(g, batch_size, config.model.det_module.num_classes, args.max_targets, device, transform)
+        else:
+            samples, targets = synthetic_batch(g, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
         total, losses = train_step(model, criterion, optimizer, samples, targets, config.optimizer.clip_max_norm)
         print('step %d  loss %.5f  %s' % (step, float(total), {k: round(float(v), 5) for k, v in sorted(losses.items())}))
         if args.steps_per_epoch > 0 and (step + 1) % args.steps_per_epoch == 0:
