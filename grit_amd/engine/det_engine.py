@@ -1,5 +1,5 @@
-"""One optimisation step of detector pre-training (reference engine/det_solver.py:58-110, without its hook machinery) and the
-optimizers it is taken with (reference train_detector.py:24-89)."""
+"""One optimisation step of detector pre-training (reference engine/det_solver.py:58-110, without its hook machinery), the
+optimizers it is taken with (reference train_detector.py:24-89) and the validation epoch (engine/det_solver.py:192-263)."""
 import torch
 from torch.optim.lr_scheduler import MultiStepLR
 
@@ -89,3 +89,36 @@ def train_step(model, criterion, optimizer, samples, targets, max_norm=0.1):
         for o in optimizers:
             o.step()
     return total.detach(), {k: v.detach() for k, v in loss_dict.items()}
+
+
+MAP_KEYS = ('map', 'map50', 'map75', 'map_small', 'map_medium', 'map_large')  # the first six COCO stats, the Valider's names
+
+
+@torch.no_grad()
+def evaluate(model, criterion, postprocessors, batches, evaluator):
+    """The reference's validation epoch (engine/det_solver.py:192-263) on one rank.  batches: an iterable of (samples, targets) on
+    the device, every target with 'image_id' and 'orig_size'; evaluator: datasets.detection.metrics.CocoEvaluator.  Per batch:
+    model -> criterion -> postprocessors['bbox'] -> evaluator.update, with no host synchronisation inside the loop; the records
+    come to the host once, in evaluator.accumulate().  Returns {'losses': the mean weighted sum, every weighted loss's mean,
+    'bbox_map', 'bbox_map50', 'bbox_map75', 'bbox_map_small', 'bbox_map_medium', 'bbox_map_large', 'result_text'}."""
+    model.eval()
+    criterion.eval()
+    sums, steps = {}, 0
+    for samples, targets in batches:
+        outputs = model(samples)
+        loss_dict = criterion(outputs, targets)
+        weighted = {k: v * criterion.weight_dict[k] for k, v in loss_dict.items() if k in criterion.weight_dict}
+        weighted['losses'] = sum(weighted.values())
+        for k, v in weighted.items():
+            sums[k] = sums[k] + v.detach() if k in sums else v.detach()
+        results = postprocessors['bbox'](outputs, torch.stack([t['orig_size'] for t in targets], dim=0))
+        evaluator.update(results, targets)
+        steps += 1
+    evaluator.synchronize_between_processes()
+    evaluator.accumulate()
+    evaluator.summarize()
+    box = evaluator.coco_eval['bbox']
+    out = {k: float(v) / steps for k, v in sums.items()}
+    out.update({'bbox_' + name: float(box.stats[i]) for i, name in enumerate(MAP_KEYS)})
+    out['result_text'] = box.result_text
+    return out

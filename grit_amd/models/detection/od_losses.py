@@ -11,8 +11,8 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from grit_amd.ops import det_eval as _det_eval
 from grit_amd.ops import det_loss as _det
-from grit_amd.utils import box_ops
 
 
 def sigmoid_focal_loss(inputs, targets, num_boxes, alpha=0.25, gamma=2):
@@ -126,17 +126,15 @@ class SetCriterion(nn.Module):
 
 
 class PostProcess(nn.Module):
-    """Model outputs -> per image the 100 best (score, label, box) with boxes in absolute corner form.  Evaluation only: plain torch."""
+    """Model outputs -> per image the 100 best (score, label, box) with boxes in absolute corner form.  The selection and the boxes
+    are grit_det_topk_f32 (grit_amd/ops/det_eval.py): it selects on the logits, the sigmoid is applied to the selected ones only."""
 
     @torch.no_grad()
     def forward(self, outputs, target_sizes):
         logits, boxes = outputs['pred_logits'], outputs['pred_boxes']
         if len(logits) != len(target_sizes) or target_sizes.shape[1] != 2:
             raise ValueError("PostProcess: target_sizes must be [batch, 2] (height, width)")
-        B, Q, K = logits.shape
-        scores, flat = logits.sigmoid().reshape(B, Q * K).topk(min(100, Q * K), dim=1)
-        query, labels = flat // K, flat % K
-        corners = box_ops.box_cxcywh_to_xyxy(boxes).gather(1, query[..., None].expand(-1, -1, 4))
-        height, width = target_sizes.unbind(1)
-        corners = corners * torch.stack([width, height, width, height], 1)[:, None, :]
+        K = logits.shape[2]
+        top_logit, top_index, corners = _det_eval.det_topk(logits.float(), boxes.float(), target_sizes.float())
+        scores, labels = top_logit.sigmoid(), top_index.to(torch.int64) % K
         return [{'scores': s, 'labels': l, 'boxes': b} for s, l, b in zip(scores, labels, corners)]

@@ -994,6 +994,59 @@ int grit_det_loss_bwd_f32(const float* logits, const float* boxes, const int64_t
                           const int32_t* tgt_offsets, const int32_t* match_t, int L, int B, int Q, int K, float alpha,
                           const float* num_boxes, const float* coef, int ldc, float* dlogits, float* dboxes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Detector evaluation (reference models/detection/od_losses.py PostProcess :326-356; datasets/detection/metrics/cocoeval.py
+ * computeIoU :172-199 and evaluateImg :252-334 for iouType 'bbox', useCats 1).  The device selects an image's best detections and
+ * matches them to its ground truth; packing, accumulation and summary are the host's (grit_amd/ops/det_eval.py,
+ * grit_amd/datasets/detection/metrics/coco_eval.py).
+ *
+ * grit_det_topk_f32: logits [B, Q, K], boxes [B, Q, 4] (cxcywh in [0, 1]), sizes [B, 2] (height, width), all fp32.  With
+ * n = Q * K and N = min(GRIT_DET_TOPK, n) it writes, per image, the N largest logits in the order logit descending, then flat index
+ * q * K + k ascending -- a function of the data alone:
+ *     top_logit [B, N] fp32, top_index [B, N] int32, out_boxes [B, N, 4] fp32 = the query's box as absolute corners,
+ *     ((cx - 0.5 w) * width, (cy - 0.5 h) * height, (cx + 0.5 w) * width, (cy + 0.5 h) * height) in fp32, uncontracted.
+ * The sigmoid is never evaluated (it is monotonic; the caller applies it to the N selected logits).  Two launches: an image's map is
+ * split over chunks = min(GRIT_DET_TOPK_CHUNKS, ceil(n / 8192)) workgroups, chunk c = the flat indices [c * len, (c + 1) * len) with
+ * len = ceil(n / chunks); each keeps its chunk's N best (radix select on the order-preserving integer image of the float), one
+ * workgroup per image sorts the chunks' candidates.  work: B * GRIT_DET_TOPK_CHUNKS * GRIT_DET_TOPK uint64 of workspace that belongs
+ * to this call.  NaN logits are outside the contract (they are ordered by their bit pattern).  n >= 2^31 or B > 65535: GRIT_ERR_BAD_ARG.
+ *
+ * grit_det_eval_img: one workgroup per image.  scores [B, N] fp32, labels [B, N] int64, boxes [B, N, 4] fp32 absolute corners, an
+ * image's rows in score order (the order grit_det_topk_f32 gives); N <= GRIT_DET_TOPK.  slot [B] int32: the image's position in the
+ * split's packed ground truth `gt` (an image with a slot outside [0, gt->n_img) is left out):
+ *     img_off [n_img + 1] int32; per annotation box [4] float64 (x, y, w, h), area float64, cat int32, crowd uint8; the annotations
+ *     of an image sorted by category, in annotation order within a category; cat_valid [n_cat] uint8; max_per_img: the largest
+ *     annotation count of an image, > GRIT_DET_MAX_SIDE gives GRIT_ERR_UNSUPPORTED.
+ * iou_thr [T] and area_rng [A, 2] float64 are the host's numbers (numpy.linspace), T <= 16, A <= 4.  All arithmetic in float64,
+ * uncontracted: a detection is (x1, y1, fp32(x2 - x1), fp32(y2 - y1)) widened, its area w * h, a ground truth's area its `area`
+ * field; IoU of D and G: w = min(D2 + D0, G2 + G0) - max(D0, G0), 0 if w <= 0, h likewise, i = w h,
+ * u = crowd ? D2 D3 : D2 D3 + G2 G3 - i, iou = i / u.  Per area range a ground truth is ignored if crowd or its area is outside
+ * (< and >), ignored ones last, stably; the detections of a category, in order, take the best free ground truth with
+ * iou >= min(t, 1 - 1e-10) by the rules of cocoeval.py:296-309; an unmatched detection with its own area outside is ignored.
+ * Records at row slot * N + n of buffers over the split (rec_rank filled with -1 by the caller before the first call):
+ *     rec_flags [n_img * N, A] uint32   bit t: matched at threshold t; bit 16 + t: ignored at threshold t
+ *     rec_rank  [n_img * N] int32       rank among the image's detections of its category; -1: label outside [0, n_cat) or with
+ *                                       cat_valid 0 (the detection does not take part)
+ *     rec_score [n_img * N] fp32, rec_label [n_img * N] int32, seen [n_img] uint8 = 1
+ * No atomics on global memory, no order dependence: two calls give identical bytes.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_DET_TOPK 100
+#define GRIT_DET_TOPK_CHUNKS 40
+typedef struct {
+    const int32_t* img_off;
+    const double* box;
+    const double* area;
+    const int32_t* cat;
+    const uint8_t* crowd;
+    const uint8_t* cat_valid;
+    int n_img, n_cat, max_per_img;
+} grit_det_gt;
+int grit_det_topk_f32(const float* logits, const float* boxes, const float* sizes, int B, int Q, int K, uint64_t* work,
+                      float* top_logit, int32_t* top_index, float* out_boxes, void* stream);
+int grit_det_eval_img(const float* scores, const int64_t* labels, const float* boxes, const int32_t* slot, int B, int N,
+                      const grit_det_gt* gt, const double* iou_thr, int T, const double* area_rng, int A, uint32_t* rec_flags,
+                      int32_t* rec_rank, float* rec_score, int32_t* rec_label, uint8_t* seen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,17 @@
 """Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
 
-    python train_detector.py --synthetic [--augment] --steps 3 [--batch-size 2] [--size 224] [--bf16] [key=value ...]
+    python train_detector.py --synthetic [--augment] --steps 3 [--batch-size 2] [--size 224] [--bf16] [--eval] [key=value ...]
 
-The Visual Genome / LMDB readers, the hook-based solver and the COCO-style evaluation are out of scope of this build, so the only
-data source here is `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
+The Visual Genome / LMDB readers and the hook-based solver are out of scope of this build, so the only data source here is
+`--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
 (grit_amd/models/detection/od_losses.py) and engine.det_engine.train_step, and prints the loss dictionary of every step.
 `--augment` feeds the input pipeline of the recipe instead of noise tensors: seeded uint8 images of mixed sizes with pixel boxes go
 through datasets.detection.make_transforms('train', 'train') -- flip, random resize, ratio resize + crop + resize -- and
 collate_detection, which resamples the batch on the device (`--size` does not apply: the recipe decides the sizes).
 `--bf16` trains on the path the captioner uses (grit_amd.amp.Bf16Compute: bf16 compute copies, fp32 masters, flat AdamW and gradient
 clipping on the device, the reference's four parameter groups and MultiStepLR; engine.det_engine.build_optimizers_schedulers).
+`--eval` evaluates after the steps (engine.det_engine.evaluate: PostProcess and the COCO-style box evaluation on the device,
+datasets.detection.metrics.CocoEvaluator) on `--eval-batches` seeded synthetic batches and prints the losses and the box mAP table.
 Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
 """
 import argparse
@@ -18,7 +20,7 @@ import random
 import torch
 
 from grit_amd.config import detection_config
-from engine.det_engine import build_optimizers_schedulers, train_step
+from engine.det_engine import build_optimizers_schedulers, evaluate, train_step
 from models.detection.detector import build_detector
 from utils.misc import NestedTensor
 
@@ -35,6 +37,24 @@ def synthetic_batch(generator, batch_size, size, num_classes, max_targets, devic
         targets.append({'labels': torch.randint(0, num_classes, (n,), generator=generator).to(device),
                         'boxes': torch.cat([centre, wh], 1).to(device)})
     return NestedTensor(images.to(device), mask.to(device), any_padding=False), targets
+
+
+def synthetic_split(generator, batches, batch_size, size, num_classes, max_targets, device):
+    """`batches` synthetic batches as an evaluation split: every target also carries 'image_id' and 'orig_size' (device tensors),
+    and the annotations -- the same boxes in pixels, (x, y, w, h), area w * h, ids from 1 -- come back as a COCO dataset dictionary."""
+    split, images, annotations = [], [], []
+    for _ in range(batches):
+        samples, targets = synthetic_batch(generator, batch_size, size, num_classes, max_targets, device)
+        for t in targets:
+            image_id = len(images) + 1
+            images.append({'id': image_id, 'height': size, 'width': size})
+            t['image_id'] = torch.tensor(image_id, device=device)
+            t['orig_size'] = torch.tensor([size, size], device=device)
+            for label, (cx, cy, w, h) in zip(t['labels'].tolist(), (t['boxes'].double() * size).tolist()):
+                annotations.append({'id': len(annotations) + 1, 'image_id': image_id, 'category_id': label,
+                                    'bbox': [cx - 0.5 * w, cy - 0.5 * h, w, h], 'area': w * h, 'iscrowd': 0})
+        split.append((samples, targets))
+    return split, {'images': images, 'categories': [{'id': c} for c in range(num_classes)], 'annotations': annotations}
 
 
 SOURCE_SIZES = ((500, 375), (375, 500), (500, 333), (640, 480), (480, 640), (400, 300))  # (w, h) of the synthetic "photos"
@@ -73,6 +93,8 @@ def main():
     ap.add_argument('--bf16', action='store_true', help='bf16 compute + fp32 masters: flat AdamW and device gradient clipping')
     ap.add_argument('--steps-per-epoch', type=int, default=0,
                     help='with --bf16: step the lr schedulers once per this many steps (0: never within a run)')
+    ap.add_argument('--eval', action='store_true', help='after the steps: losses and COCO-style box mAP on seeded synthetic batches')
+    ap.add_argument('--eval-batches', type=int, default=2)
     ap.add_argument('overrides', nargs='*', help='dotted key=value configuration overrides')
     args = ap.parse_args()
     if not args.synthetic:
@@ -91,7 +113,7 @@ def main():
     config = detection_config(**over)
     torch.manual_seed(config.exp.seed)
     device = torch.device('cuda')
-    model, criterion, _ = build_detector(config)
+    model, criterion, postprocessors = build_detector(config)
     model.to(device)
     schedulers = []
     if args.bf16:
@@ -116,6 +138,13 @@ def main():
         if args.steps_per_epoch > 0 and (step + 1) % args.steps_per_epoch == 0:
             for sch in schedulers:
                 sch.step()
+    if args.eval:
+        from datasets.detection.metrics import AnnotationIndex, CocoEvaluator
+        split, dataset = synthetic_split(g, args.eval_batches, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
+        result = evaluate(model, criterion, postprocessors, split, CocoEvaluator(AnnotationIndex(dataset), ('bbox',), device=device))
+        text = result.pop('result_text')
+        print('eval  %s' % {k: round(v, 5) for k, v in sorted(result.items())})
+        print(text, end='')
 
 
 def _plain_optimizer(model, config):
