@@ -49,7 +49,12 @@ _DEFAULTS = {
                       sc_backbone_lr=5e-6, weight_decay=0.01, beta_1=0.9, beta_2=0.99, batch_size=16, num_workers=2,
                       freezing_xe_epochs=0, freezing_sc_epochs=0, finetune_xe_epochs=10, finetune_sc_epochs=10,
                       freeze_detector=False, freeze_backbone=False,
-                      sc_reward='host'),  # 'device': CIDEr-D of the beams in one kernel launch (grit_amd/ops/cider.py), no host round trip
+                      sc_reward='host',  # 'device': CIDEr-D of the beams in one kernel launch (grit_amd/ops/cider.py), no host round trip
+                      # what the self-critical step decodes: 'beam' = the reference's beam search with gradient; 'sample' = sc_samples
+                      # independent samples per image (None: model.beam_size) at sc_temperature, the mean reward of an image's samples
+                      # as the baseline.  Only temperature 1 (and no truncation, which the step never applies) samples the policy
+                      # itself, i.e. gives an unbiased policy gradient; any other temperature trains on a tempered proposal.
+                      sc_decode='beam', sc_samples=None, sc_temperature=1.0),
 }
 
 

@@ -346,12 +346,25 @@ def train_sc_step(model, batch, optimizers, reward_fn, config):
     WITH gradient (out_size = beam_size) -> host reward -> loss -> backward -> barrier -> Adam x2.
     reward_fn(tokens [B, beam, T] int64, batch) -> float tensor [B, beam] on the model's device: in the reference it is
     CIDEr-D of the decoded, PTB-tokenised beams against the ground-truth captions (:433-438), a host-side (Java)
-    component that the caller supplies.  Returns (loss, mean reward, mean baseline) as detached device tensors."""
+    component that the caller supplies.  Returns (loss, mean reward, mean baseline) as detached device tensors.
+    config.optimizer.sc_decode = 'sample' replaces the beams by sc_samples independent samples per image at sc_temperature (no
+    truncation; the seed comes from torch's device generator): the same shapes, reward and loss, the baseline being the mean
+    reward of an image's samples."""
     beam_size, seq_len = config.model.beam_size, config.model.beam_len
+    opt = getattr(config, 'optimizer', None)
+    sc_decode = getattr(opt, 'sc_decode', 'beam')
+    if sc_decode not in ('beam', 'sample'):
+        raise ValueError("optimizer.sc_decode must be 'beam' or 'sample', not %r" % (sc_decode,))
     optimizers['model'].zero_grad()
     optimizers['backbone'].zero_grad()
-    outs, log_probs = model(batch['samples'], seq=None, use_beam_search=True, max_len=seq_len, eos_idx=config.model.eos_idx,
-                            beam_size=beam_size, out_size=beam_size, return_probs=False)
+    if sc_decode == 'sample':
+        beam_size = getattr(opt, 'sc_samples', None) or beam_size
+        outs, log_probs = model(batch['samples'], seq=None, use_beam_search=True, max_len=seq_len, eos_idx=config.model.eos_idx,
+                                beam_size=beam_size, out_size=beam_size, decode='sample',
+                                temperature=getattr(opt, 'sc_temperature', 1.0))
+    else:
+        outs, log_probs = model(batch['samples'], seq=None, use_beam_search=True, max_len=seq_len, eos_idx=config.model.eos_idx,
+                                beam_size=beam_size, out_size=beam_size, return_probs=False)
     reward = reward_fn(outs.detach(), batch).to(log_probs.device, torch.float32).view(outs.shape[0], beam_size)
     loss, baseline = sc_loss(log_probs, reward)
     loss.backward()

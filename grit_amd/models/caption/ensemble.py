@@ -97,6 +97,10 @@ class Ensemble(BeamSearchSteps, nn.Module):
         if not use_beam_search:
             raise NotImplementedError("Ensemble only decodes by beam search (use_beam_search=True): the reference has no "
                                       "teacher-forcing ensemble")
+        decode = kwargs.pop('decode', 'beam')  # Transformer.forward's switch; the signature here stays the reference's
+        if decode != 'beam':
+            raise NotImplementedError("Ensemble only decodes by beam search: decode=%r is for a single Transformer (sampling from "
+                                      "an average of distributions is not built)" % (decode,))
         self._check_placement()
         feats = self._member_features(samples)
         if self._graph_eligible(feats, return_probs, kwargs):

@@ -47,6 +47,8 @@
  *                           finished-beam masking, candidate scores, selection, beam / word split, score / mask / log-prob gathers
  *   grit_beam_step_mean_f32 <- the same after the averaged word log-probabilities of an ensemble (models/caption/ensemble.py:128-214:
  *                           torch.mean(torch.stack(per_model), 0) followed by the body of `iter`)
+ *   grit_sample_step_f32 <- nothing in the reference (it decodes by beam search only): one word per row drawn from the tempered,
+ *                           top-k / nucleus truncated word distribution, in integer arithmetic that a host form repeats exactly
  *   grit_decode_step_inputs <- CaptionGenerator.get_seq_inputs in stateful mode + the word / position embedding sum
  *                           (models/caption/cap_generator.py:116-137,148)
  *   grit_kv_append       <- running_keys / running_values of the stateful self-attention (models/common/attention.py:166-181) and
@@ -58,7 +60,8 @@
  *                           cider.compute_score) and datasets/caption/metrics/cider/cider_scorer.py (counts2vec, sim, compute_cider)
  *   grit_caption_scores  <- the evaluation's scores, engine/caption_engine.py:165-190 (decode, itertools.groupby, PTBTokenizer.tokenize,
  *                           compute_scores) and datasets/caption/metrics/{bleu/bleu_scorer.py, rouge/rouge.py, cider/cider_scorer.py}
- * (none of the last thirteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops)
+ * (none of the last fourteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
 #define GRIT_HIP_H
@@ -69,7 +72,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 52
+#define GRIT_ABI_VERSION 53
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -782,6 +785,41 @@ int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const
                             const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace,
                             long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
                             float* picked_logprob, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * One step of sampled decoding after the decoder (no ancestor in the reference, whose only decoder is beam search): one word per
+ * output row, drawn from softmax(logp * inv_temperature) restricted to the top_k most probable words and then to the smallest
+ * nucleus of mass top_p.  Output row r reads row r / fan of logp [rows / fan, V] float32 (row stride ld elements): at the first
+ * step the decoder ran on one row per image and fan = samples per image, afterwards fan = 1.  prev_words [rows] int64 and alive_in
+ * [rows] float32 are NULL together: NULL = first step, every row alive.  top_p_q32 = round(top_p * 2^32) in [1, 2^32].  seed_dev
+ * points to ONE uint64 in device memory.  Outputs, all [rows]: words int64, picked float32, alive_out float32.
+ *
+ * The choice is a function of the stored bits of logp, *seed_dev, r and step and of nothing else (no atomics, no workspace, no host
+ * state), so a captured HIP graph replays it and a host form (grit_amd/ops/sample.py: sample_step_host) repeats it bit for bit:
+ *   0. alive = alive_in[r] * (prev_words[r] != eos).  0: words = fill, picked = +0.0, alive_out = 0, done.  Otherwise alive_out = 1.
+ *   1. m = max_i logp_i.
+ *   2. t_i = ((logp_i - m) * inv_temperature) * log2e, three rounded fp32 operations (log2e = 0x3FB8AA3B);
+ *      k_i = floor(t_i), f_i = t_i - k_i.
+ *   3. p_i = P(f_i) ~ 2^f: degree 6, Horner in fp32, every multiply and add rounded, coefficients (constant first) 0x3F800000,
+ *      0x3F317216, 0x3E75FEAD, 0x3D634478, 0x3C1E8620, 0x3AA36993, 0x3962A320.  P(0) = 1 and P(1) = 2 exactly, P is monotone on
+ *      [0, 1], largest relative error 8.6e-8.
+ *   4. w_i = trunc(p_i * 2^(40 + k_i)) as uint64; 0 when 40 + k_i < -1 and for logp_i = -inf.  The largest weight is 2^40.
+ *   5. order: i before j iff logp_i > logp_j, or they are equal and i < j.  K = top_k > 0 ? min(top_k, V) : V; S_K = the weight
+ *      sum of the first K in that order.
+ *   6. need = max(1, (top_p_q32 * S_K) >> 32) (128-bit product); kept = the shortest prefix of the first K whose weight sum is
+ *      >= need, at least one word; a boundary inside a group of equal log-probs is resolved by index.  S = the kept sum.
+ *   7. c = *seed_dev + 0x9E3779B97F4A7C15 * (r * 4096 + step + 1) mod 2^64, x = splitmix64's finaliser of c
+ *      (x ^= x >> 30, x *= 0xBF58476D1CE4E5B9, x ^= x >> 27, x *= 0x94D049BB133111EB, x ^= x >> 31), target = (x * S) >> 64.
+ *   8. word = the smallest kept i whose cumulative kept weight, summed in INDEX order, exceeds target.
+ *   9. picked = logp[word] as stored: the model's log-prob, not the tempered or truncated one.
+ * NaN or +inf log-probs and a live row without a finite entry are outside the contract: the word is then unspecified but in
+ * [0, V), and nothing out of bounds is read or written.  Limits: 1 <= V <= GRIT_SAMPLE_MAX_V (UNSUPPORTED above), ld >= V,
+ * fan >= 1, rows % fan == 0, 0 <= step < 4096, top_k >= 0, inv_temperature finite and > 0.  One launch, a workgroup per row.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_SAMPLE_MAX_V 16384
+int grit_sample_step_f32(const float* logp, long ld, int rows, int fan, int V, const int64_t* prev_words, const float* alive_in,
+                         int eos, int fill, float inv_temperature, int top_k, unsigned long long top_p_q32,
+                         const uint64_t* seed_dev, int step, int64_t* words, float* picked, float* alive_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Gated merge of the grid / region cross-attentions of a caption decoder layer, inference only (reference

@@ -53,6 +53,17 @@ def caption_tokens(model, image, config, beam_size=None):
 
 
 @torch.inference_mode()
+def sample_tokens(model, image, config, n, temperature=1.0, top_k=0, top_p=1.0, seed=None):
+    """image [3,H,W] (already normalised) -> (tokens [n, beam_len] int64, log_probs [n, beam_len]): n captions drawn from the
+    model's distribution (Transformer.forward(decode='sample')) instead of the best beam."""
+    device = next(model.parameters()).device
+    images = nested_tensor_from_tensor_list([image]).to(device)
+    tokens, log_probs = model(images, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
+                              beam_size=n, out_size=n, decode='sample', temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+    return tokens[0], log_probs[0]
+
+
+@torch.inference_mode()
 def caption_stream(model, batches, config, beam_size=None):
     """Caption a sequence of batches (NestedTensor each), yielding (tokens, log_probs) per batch in order -- the inner loop
     of evaluate_metrics (reference engine/caption_engine.py:156-175) arranged for the GPU: the detector of batch i+1 is
@@ -158,6 +169,11 @@ def run_main():
     ap.add_argument('--checkpoint', nargs='+', default=[''], help="one checkpoint, or several for an ensemble")
     ap.add_argument('--vocab', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'vocab.json'))
     ap.add_argument('--beam', type=int, default=None)
+    ap.add_argument('--sample', type=int, default=0, metavar='N', help="print N sampled captions instead of the best beam")
+    ap.add_argument('--temperature', type=float, default=1.0)
+    ap.add_argument('--top-k', type=int, default=0, help="sample among the k most probable words only (0: all)")
+    ap.add_argument('--top-p', type=float, default=1.0, help="sample inside the smallest nucleus of this mass")
+    ap.add_argument('--seed', type=int, default=None, help="sampling seed (default: torch's device generator)")
     a = ap.parse_args()
     config = default_config()
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
@@ -171,6 +187,11 @@ def run_main():
         rgb = np.asarray(Image.open(a.img).convert('RGB'), dtype=np.float32) / 255.0
         mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
         image = torch.from_numpy(((rgb - mean) / std).transpose(2, 0, 1))
+    if a.sample > 0:
+        tokens, _ = sample_tokens(model, image, config, a.sample, a.temperature, a.top_k, a.top_p, a.seed)
+        for line in (decode(tokens, a.vocab, config.model.eos_idx) if os.path.exists(a.vocab) else tokens.tolist()):
+            print(line)
+        return
     tokens, _ = caption_tokens(model, image, config, a.beam)
     print(decode(tokens, a.vocab, config.model.eos_idx)[0] if os.path.exists(a.vocab) else tokens.tolist())
 
