@@ -40,6 +40,10 @@ _DEFAULTS = {
                     transform_cfg=dict(size=[384, 640], resize_name='maxwh', randaug=False)),  # reference yaml: randaug true (host-side PIL); 'device' runs the same operations on the GPU
     'model': dict(
         use_gri_feat=True, use_reg_feat=True, grid_feat_dim=1024, frozen_stages=2, beam_size=5, beam_len=20,
+        # beam-search constraints of evaluation and inference (Transformer.forward; all off, as in the reference): at least
+        # beam_min_len words before <eos>, no n-gram of beam_no_repeat_ngram words twice, no word twice in a row, vocabulary ids that
+        # are never chosen, final ranking by score / length^beam_length_penalty.  Self-critical training decodes unconstrained.
+        beam_min_len=0, beam_no_repeat_ngram=0, beam_no_repeat_word=False, beam_suppress=[], beam_length_penalty=0.0,
         dropout=0.2, attn_dropout=0.2, vocab_size=10201, max_len=54, pad_idx=1, bos_idx=2, eos_idx=3, d_model=512,
         n_heads=8, grid_net=dict(n_memories=1, n_layers=3), cap_generator=dict(decoder_name='parallel', n_layers=3),
         detector=dict(checkpoint='', d_model=512, dim_feedforward=1024, num_heads=8, num_layers=6, num_levels=4,
@@ -56,6 +60,15 @@ _DEFAULTS = {
                       # itself, i.e. gives an unbiased policy gradient; any other temperature trains on a tempered proposal.
                       sc_decode='beam', sc_samples=None, sc_temperature=1.0),
 }
+
+
+def beam_constraints(config):
+    """The model.beam_* constraint keys as keyword arguments of Transformer.forward / Ensemble.forward; a config written before
+    they existed gives the defaults (all off)."""
+    m = config.model
+    return dict(min_len=getattr(m, 'beam_min_len', 0), no_repeat_ngram=getattr(m, 'beam_no_repeat_ngram', 0),
+                no_repeat_word=getattr(m, 'beam_no_repeat_word', False), suppress=tuple(getattr(m, 'beam_suppress', None) or ()),
+                length_penalty=getattr(m, 'beam_length_penalty', 0.0))
 
 
 def default_config(**overrides):

@@ -116,6 +116,7 @@ constexpr int kMaxMaps = 8;
 struct MapTable { const float* p[kMaxMaps]; };  // by value in the kernel arguments: nothing to upload, nothing to keep alive
 
 struct OneMap {
+    static constexpr bool kBans = false;
     const float* p;
     __device__ __forceinline__ float at(size_t i) const { return p[i]; }
     __device__ __forceinline__ bool aligned16(size_t i) const { return (((uintptr_t)(p + i)) & 15) == 0; }
@@ -123,6 +124,7 @@ struct OneMap {
 };
 
 struct MeanMaps {
+    static constexpr bool kBans = false;
     MapTable t;
     int n;
     float factor;
@@ -160,6 +162,43 @@ struct MeanMaps {
     }
 };
 
+// The constrained step (grit_beam_step_con_f32): a source of word log-probabilities plus the rules that ban words per beam.  All of
+// it travels by value in the kernel arguments.  Only stage 1 reads the rules; stage 2 runs on the plain source.
+constexpr int kMaxHistory = GRIT_BEAM_MAX_HISTORY, kMaxSuppress = GRIT_BEAM_MAX_SUPPRESS, kMaxSlice = GRIT_BEAM_MAX_SLICE;
+struct Bans {
+    const int64_t* hist;  // [rows, t], row stride hist_ld
+    long hist_ld;
+    int t, ngram, repeat_word, eos_word /* -1: <eos> allowed */, n_sup;
+    int sup[kMaxSuppress];
+};
+
+template <class Base>
+struct Banned : Base {
+    static constexpr bool kBans = true;
+    Bans bans;
+};
+
+// The banned words of one live beam row as a bitmap over the workgroup's vocabulary slice [v0, v1): a thread per history
+// position finds the n-gram continuations, further threads add the fixed rules.  The caller synchronises afterwards.
+__device__ __forceinline__ void mark_bans(const Bans& c, int row_id, int v0, int v1, int64_t* hist, unsigned* bits) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < (v1 - v0 + 31) >> 5; w += kBeamThreads) bits[w] = 0u;
+    if (tid < c.t) hist[tid] = c.hist[(size_t)row_id * c.hist_ld + tid];
+    __syncthreads();
+    auto ban = [&](int64_t word) {
+        if (word >= v0 && word < v1) atomicOr(&bits[(int)(word - v0) >> 5], 1u << ((int)(word - v0) & 31));  // LDS
+    };
+    const int n = c.ngram, t = c.t;
+    if (n >= 1 && tid <= t - n) {  // the n - 1 words from position tid against the last n - 1
+        bool same = true;
+        for (int q = 0; q < n - 1; ++q) same = same && hist[tid + q] == hist[t - n + 1 + q];
+        if (same) ban(hist[tid + n - 1]);
+    }
+    if (tid >= 64 && tid < 64 + c.n_sup) ban(c.sup[tid - 64]);
+    if (tid == 128 && c.repeat_word && t >= 1) ban(hist[t - 1]);
+    if (tid == 129 && c.eos_word >= 0) ban(c.eos_word);
+}
+
 template <int KL, class Src>  // per-thread list length: k <= KL <= kMaxK (5 for the usual beam of 5: 40 % fewer compare-swaps per insertion)
 __global__ __launch_bounds__(kBeamThreads)
 void beam_partial(Src logp, long ld, const float* __restrict__ seq_lp, const float* __restrict__ seq_mask,
@@ -192,7 +231,33 @@ void beam_partial(Src logp, long ld, const float* __restrict__ seq_lp, const flo
             }
     };
     const int flat0 = j * V;
-    if (alive) {
+    if constexpr (Src::kBans) {
+        // a live beam under constraints: the slice's banned words score -inf and stay candidates with their own index (a finished
+        // beam has no bans and takes the branch below)
+        __shared__ int64_t hist[kMaxHistory];
+        __shared__ unsigned bits[kMaxSlice / 32];
+        if (alive && v0 < v1) {  // uniform over the workgroup
+            mark_bans(logp.bans, row_id, v0, v1, hist, bits);
+            __syncthreads();
+            auto score = [&](float x, unsigned banned) { return banned ? -INFINITY : base + x; };
+            if (logp.aligned16(row + v0)) {
+                const int n4 = (v1 - v0) >> 2;
+                for (int i = tid; i < n4; i += kBeamThreads) {
+                    const float4 t = logp.at4(row + v0 + 4 * i);
+                    const int e = flat0 + v0 + 4 * i;
+                    const unsigned m = bits[(4 * i) >> 5] >> ((4 * i) & 31);  // four neighbours share a bitmap word
+                    push(score(t.x, m & 1u), e); push(score(t.y, m & 2u), e + 1);
+                    push(score(t.z, m & 4u), e + 2); push(score(t.w, m & 8u), e + 3);
+                }
+                for (int v = v0 + 4 * n4 + tid; v < v1; v += kBeamThreads)
+                    push(score(logp.at(row + v), (bits[(v - v0) >> 5] >> ((v - v0) & 31)) & 1u), flat0 + v);
+            } else {
+                for (int v = v0 + tid; v < v1; v += kBeamThreads)
+                    push(score(logp.at(row + v), (bits[(v - v0) >> 5] >> ((v - v0) & 31)) & 1u), flat0 + v);
+            }
+        }
+    }
+    if (alive && !Src::kBans) {
         const bool vec = logp.aligned16(row + v0);
         if (vec) {
             const int n4 = (v1 - v0) >> 2;
@@ -205,7 +270,7 @@ void beam_partial(Src logp, long ld, const float* __restrict__ seq_lp, const flo
         } else {
             for (int v = v0 + tid; v < v1; v += kBeamThreads) push(base + logp.at(row + v), flat0 + v);
         }
-    } else {
+    } else if (!alive) {
         // a finished beam survives only through vocabulary index 0; the other entries all score -999 (ties by index)
         const int v = v0 + tid;  // the k <= 8 best of the slice are among its first entries
         if (v < v1) push(v == 0 ? base : -999.f, flat0 + v);
@@ -280,10 +345,11 @@ extern "C" long grit_beam_step_workspace(int B, int cur_beam, int k) {
 
 namespace {
 
-template <class Src>
+template <class Src, class Part = Src>  // Part: what stage 1 reads, Src itself or Banned<Src>
 int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos, int first_step,
               int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
+              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream,
+              const Bans* bans = nullptr) {
     if (!seq_logprob || !workspace || !sel_beam || !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob ||
         B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V)
         return GRIT_ERR_BAD_ARG;
@@ -292,13 +358,21 @@ int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask,
     if (k > kMaxK || (long)k > (long)cur_beam * V || cur_beam * parts * k > 128 || (long)cur_beam * V > 0x7fffffffL || B > 65535)
         return GRIT_ERR_UNSUPPORTED;
     if (workspace_bytes < grit_beam_step_workspace(B, cur_beam, k)) return GRIT_ERR_BAD_ARG;
+    Part part;
+    if constexpr (Part::kBans) {
+        if ((((V + parts - 1) / parts + 3) & ~3) > kMaxSlice) return GRIT_ERR_UNSUPPORTED;  // the ban bitmap of a slice
+        static_cast<Src&>(part) = src;
+        part.bans = *bans;
+    } else {
+        part = src;
+    }
     float* ws_val = reinterpret_cast<float*>(workspace);
     int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)B * cur_beam * parts * kMaxK);
     if (k <= 5)
-        hipLaunchKernelGGL((beam_partial<5, Src>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld,
+        hipLaunchKernelGGL((beam_partial<5, Part>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part, ld,
                            seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
     else
-        hipLaunchKernelGGL((beam_partial<kMaxK, Src>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld,
+        hipLaunchKernelGGL((beam_partial<kMaxK, Part>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part, ld,
                            seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
     hipLaunchKernelGGL(beam_merge<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_mask, prev_words, eos, first_step,
                        cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob);
@@ -335,6 +409,43 @@ extern "C" int grit_beam_step_mean_f32(const float* const* maps, int n_maps, lon
     src.factor = (float)outputs / (float)(outputs * n_maps);
     return beam_step(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace, workspace_bytes,
                      sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
+}
+
+extern "C" int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                                      const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                                      const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
+                                      int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
+                                      int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
+                                      float* picked_logprob, void* stream) {
+    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0 || t < 0 || no_repeat_ngram < 0 || n_suppress < 0 ||
+        (n_suppress > 0 && !suppress) || (t > 0 && (!history || history_ld < t)) || (ban_eos && (eos < 0 || eos >= V)))
+        return GRIT_ERR_BAD_ARG;
+    if (n_maps > kMaxMaps || t > kMaxHistory || n_suppress > kMaxSuppress) return GRIT_ERR_UNSUPPORTED;
+    Bans bans{};
+    bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
+    bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
+    bans.n_sup = n_suppress;
+    for (int i = 0; i < n_suppress; ++i) {
+        if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
+        bans.sup[i] = suppress[i];
+    }
+    if (n_maps == 1) {
+        if (!maps[0]) return GRIT_ERR_BAD_ARG;
+        return beam_step<OneMap, Banned<OneMap>>(OneMap{maps[0]}, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam,
+                                                 V, k, workspace, workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
+                                                 picked_logprob, stream, &bans);
+    }
+    MeanMaps src{};
+    for (int m = 0; m < n_maps; ++m) {
+        if (!maps[m]) return GRIT_ERR_BAD_ARG;
+        src.t.p[m] = maps[m];
+    }
+    src.n = n_maps;
+    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
+    src.factor = (float)outputs / (float)(outputs * n_maps);
+    return beam_step<MeanMaps, Banned<MeanMaps>>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k,
+                                                 workspace, workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
+                                                 picked_logprob, stream, &bans);
 }
 
 extern "C" int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t* idx_out, float* val_out, void* stream) {

@@ -35,10 +35,17 @@ class BeamSearchSteps(object):
     seq_logprob, log_probs, selected_words (and all_log_probs) of the running search; `members` are the captioners whose
     registered states follow the surviving beams (the Transformer itself, or every model of an ensemble)."""
 
-    def _beam_result(self, outputs, batch_size, beam_size, max_len, out_size, return_probs):
-        _, order = torch.sort(self.seq_logprob, 1, descending=True)
+    def _beam_result(self, outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx=None, length_penalty=0.0):
+        outputs = torch.cat(outputs, -1)
+        scores = self.seq_logprob
+        if length_penalty != 0:
+            # the final ranking only: score / L^alpha, L = words up to and including the first <eos> (max_len without one)
+            is_eos = outputs == eos_idx
+            length = torch.where(is_eos.any(-1), is_eos.long().argmax(-1) + 1, torch.full_like(outputs[..., 0], max_len))
+            scores = scores / length.float().pow(float(length_penalty)).unsqueeze(-1)
+        _, order = torch.sort(scores, 1, descending=True)
         idx = order.expand(batch_size, beam_size, max_len)
-        outputs = torch.gather(torch.cat(outputs, -1), 1, idx)
+        outputs = torch.gather(outputs, 1, idx)
         log_probs = torch.gather(torch.cat(self.log_probs, -1), 1, idx)
         outputs, log_probs = outputs.contiguous()[:, :out_size], log_probs.contiguous()[:, :out_size]
         if out_size == 1:
@@ -82,9 +89,10 @@ class BeamSearchSteps(object):
         return fn
 
     def _beam_advance(self, members, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size, eos_idx,
-                      **kwargs):
+                      constraints=None, **kwargs):
         """The body of `iter` after the word log-probabilities word_logprob [B, cur_beam, V]: `fused` holds what the fused step
-        returned (sel_beam, sel_word, seq_logprob, seq_mask, picked), or is None for the composed torch form."""
+        returned (sel_beam, sel_word, seq_logprob, seq_mask, picked), or is None for the composed torch form.  `constraints`
+        (ops/beam.py) bans words per live beam; `outputs` then holds the history as one tensor (`_history`)."""
         cur_beam = 1 if timestep == 0 else beam_size
         if fused is not None:
             selected_beam, selected_words, seq_logprob, seq_mask, picked = fused
@@ -98,6 +106,11 @@ class BeamSearchSteps(object):
                 frozen = self.seq_logprob.expand_as(candidates).contiguous()
                 frozen[:, :, 1:] = -999  # a finished beam survives only through vocabulary index 0
                 candidates = self.seq_mask * candidates + frozen * (1 - self.seq_mask)
+            if constraints is not None:
+                history = outputs[0] if outputs else candidates.new_zeros(candidates.shape[:2] + (0,), dtype=torch.long)
+                banned = beam_ops.banned_words_host(history, self.seq_mask if timestep > 0 else None, timestep, eos_idx, V,
+                                                    **constraints._asdict())
+                candidates = candidates.masked_fill(banned, float('-inf'))
 
             selected_idx, selected_logprob = self.select(timestep, candidates, beam_size, **kwargs)
             selected_beam = torch.div(selected_idx, V, rounding_mode='floor')
@@ -130,6 +143,12 @@ class BeamSearchSteps(object):
         self.log_probs.append(picked)
         self.selected_words = selected_words.view(-1, 1)
         return outputs
+
+    @staticmethod
+    def _history(outputs):
+        """The token history [B, cur_beam, t] as the one tensor that a constrained step reads: the concatenation that
+        `_beam_advance` would do for its gather, done ahead of the step (and then not again)."""
+        return [torch.cat(outputs, -1)] if len(outputs) > 1 else outputs
 
 
 class Transformer(BeamSearchSteps, BaseCaptioner):
@@ -175,22 +194,34 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         return vis
 
     def forward(self, images, seq, use_beam_search=False, max_len=20, eos_idx=3, beam_size=5, out_size=1,
-                return_probs=False, decode='beam', temperature=1.0, top_k=0, top_p=1.0, seed=None, **kwargs):
-        """decode='sample' (with use_beam_search=True): `beam_size` independent samples per image from the word distribution at
+                return_probs=False, decode='beam', temperature=1.0, top_k=0, top_p=1.0, seed=None, min_len=0, no_repeat_ngram=0,
+                no_repeat_word=False, suppress=(), length_penalty=0.0, **kwargs):
+        """Beam search under constraints (ops/beam.py): at least `min_len` words before <eos>, no n-gram of `no_repeat_ngram`
+        words twice, no word twice in a row (`no_repeat_word`), the ids of `suppress` never; `length_penalty` = alpha ranks the
+        final hypotheses by score / length^alpha.  All off by default.
+        decode='sample' (with use_beam_search=True): `beam_size` independent samples per image from the word distribution at
         `temperature`, truncated to the `top_k` most probable words (0: all) and to the nucleus of mass `top_p`; `seed` is an
         integer, or None for a seed from torch's device generator.  Returns tokens and log-probs [B, out_size, max_len]."""
         if not use_beam_search:
             return self.cap_generator(seq, self._visual_inputs(images))
+        constraints = beam_ops.constraints(self.cap_generator.fc.weight.shape[0], min_len, no_repeat_ngram, no_repeat_word, suppress)
+        length_penalty = float(length_penalty or 0.0)
+        if length_penalty < 0:
+            raise ValueError("length_penalty must be >= 0, not %g" % length_penalty)
         if decode == 'sample':
+            if constraints is not None or length_penalty != 0:
+                raise NotImplementedError("decode='sample' takes no beam-search constraints and no length penalty")
             if return_probs or kwargs:
                 raise NotImplementedError("decode='sample' returns the sampled words' log-probs only and takes no further arguments")
             return self.sample_decode(images, max_len, eos_idx, beam_size, out_size, temperature, top_k, top_p, seed)
         if decode != 'beam':
             raise ValueError("decode must be 'beam' or 'sample', not %r" % (decode,))
-        return self.beam_search(images, max_len, eos_idx, beam_size, out_size, return_probs, **kwargs)
+        return self.beam_search(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
+                                length_penalty=length_penalty, **kwargs)
 
     # ------------------------------------------------------------------ beam search
-    def beam_search(self, images, max_len, eos_idx, beam_size, out_size, return_probs, **kwargs):
+    def beam_search(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
+                    **kwargs):
         """Inference on a HIP device (no autograd, eval mode): the decode loop -- grid net + `max_len` decoder steps + beam
         bookkeeping, ~5 000 small kernels whose launches bound the loop at ~2.7 ms of host time per step -- is captured ONCE per
         (batch, beam, length, feature shapes) into a HIP graph and replayed from then on (next-row N1: the device-side beam
@@ -198,10 +229,12 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         (self-critical: beam search with gradient), CPU runs and return_probs keep the eager loop."""
         if self._graph_eligible(images, return_probs, kwargs):
             vis = images if self.cached_features else self.detector(images)
-            return self._beam_search_graphed(dict(vis), max_len, eos_idx, beam_size, out_size)
+            return self._beam_search_graphed(dict(vis), max_len, eos_idx, beam_size, out_size, constraints=constraints,
+                                             length_penalty=length_penalty)
         from grit_amd.ops.linear import suspend_single_use
         with suspend_single_use():  # with gradient (self-critical training) the decoder's weights are used once per STEP
-            return self._beam_search_eager(images, max_len, eos_idx, beam_size, out_size, return_probs, **kwargs)
+            return self._beam_search_eager(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
+                                           length_penalty=length_penalty, **kwargs)
 
     def _graph_eligible(self, images, return_probs, kwargs):
         if not _GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
@@ -217,12 +250,15 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         finally:
             self.cached_features = was
 
-    def _beam_search_graphed(self, vis, max_len, eos_idx, beam_size, out_size, sampling=None, seed=None):
+    def _beam_search_graphed(self, vis, max_len, eos_idx, beam_size, out_size, sampling=None, seed=None, constraints=None,
+                             length_penalty=0.0):
         """sampling = (temperature, top_k, top_p) captures the sampled decode instead: part of the key, with the seed in a static
-        device tensor that is rewritten from `seed` (a one-element device tensor) before every replay."""
+        device tensor that is rewritten from `seed` (a one-element device tensor) before every replay.  The constraint tuple and
+        the length penalty of a beam search are part of the key as well: they are baked into the captured launches."""
         def decode(feats, static_seed):
             if sampling is None:
-                return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, False)
+                return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, False, constraints=constraints,
+                                               length_penalty=length_penalty)
             return self._sample_eager(feats, max_len, eos_idx, beam_size, out_size, *sampling, static_seed)
 
         names = sorted(k for k, v in vis.items() if isinstance(v, torch.Tensor))
@@ -230,7 +266,8 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         # in-place writers -- optimizer steps, load_state_dict -- need no invalidation.  What does: parameter STORAGE being
         # replaced (module.to(dtype), Bf16Compute wrapping): the addresses of the first and last decoder parameters are in the key.
         probe = (self.grid_net.fc.weight, self.cap_generator.fc.weight)
-        key = (max_len, eos_idx, beam_size, out_size, sampling, torch.is_inference_mode_enabled(), vis[names[0]].device.index) + \
+        key = (max_len, eos_idx, beam_size, out_size, sampling, constraints, length_penalty, torch.is_inference_mode_enabled(),
+               vis[names[0]].device.index) + \
             tuple((p.data_ptr(), p.dtype) for p in probe) + \
             tuple((k, tuple(vis[k].shape), vis[k].dtype) for k in names)
         entry = self._decode_graphs.pop(key, None)
@@ -260,7 +297,8 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         graph.replay()
         return tuple(o.clone() for o in static_out)
 
-    def _beam_search_eager(self, images, max_len, eos_idx, beam_size, out_size, return_probs, **kwargs):
+    def _beam_search_eager(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
+                           **kwargs):
         batch_size, device = self.get_bs_device(images)
         self.seq_mask = torch.ones((batch_size, beam_size, 1), device=device)      # 1 while the beam is alive
         self.seq_logprob = torch.zeros((batch_size, 1, 1), device=device)          # running score per beam
@@ -271,8 +309,9 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         with self._decode_session(batch_size):
             for t in range(max_len):
                 images, outputs = self.iter(timestep=t, samples=images, outputs=outputs, return_probs=return_probs,
-                                            batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, **kwargs)
-        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs)
+                                            batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, constraints=constraints,
+                                            **kwargs)
+        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty)
 
     # ------------------------------------------------------------------ sampled decoding
     def sample_decode(self, images, max_len, eos_idx, n_samples, out_size, temperature, top_k, top_p, seed):
@@ -366,17 +405,23 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
     def _kv_cached_modules(self):
         return [layer.self_att for layer in self.cap_generator.layers]
 
-    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, **kwargs):
+    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, **kwargs):
         cur_beam = 1 if timestep == 0 else beam_size
         word_logprob = self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)
         word_logprob = word_logprob.view(batch_size, cur_beam, -1)
         fused = None
+        if constraints is not None:
+            outputs = self._history(outputs)
         if _FUSED_BEAM_STEP and not return_probs and not kwargs and beam_ops.supported(word_logprob, cur_beam, beam_size):
             # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py)
-            fused = beam_ops.beam_step(word_logprob, self.seq_logprob, self.seq_mask if timestep > 0 else None,
-                                       self.selected_words if timestep > 0 else None, eos_idx, beam_size)
+            state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
+                     eos_idx, beam_size)
+            if constraints is None:
+                fused = beam_ops.beam_step(word_logprob, *state)
+            else:  # None beyond the kernel's limits: the composed form below
+                fused = beam_ops.beam_step_con([word_logprob], *state, outputs[0] if outputs else None, timestep, constraints)
         outputs = self._beam_advance((self,), timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
-                                     eos_idx, **kwargs)
+                                     eos_idx, constraints=constraints, **kwargs)
         return samples, outputs
 
     def _follow_beams(self, selected_beam, cur_beam, batch_size, beam_size):

@@ -47,6 +47,8 @@
  *                           finished-beam masking, candidate scores, selection, beam / word split, score / mask / log-prob gathers
  *   grit_beam_step_mean_f32 <- the same after the averaged word log-probabilities of an ensemble (models/caption/ensemble.py:128-214:
  *                           torch.mean(torch.stack(per_model), 0) followed by the body of `iter`)
+ *   grit_beam_step_con_f32 <- nothing in the reference (its search cannot be steered): the same step, of one map or of the mean,
+ *                           with a per-beam set of banned words applied while the candidates are scored
  *   grit_sample_step_f32 <- nothing in the reference (it decodes by beam search only): one word per row drawn from the tempered,
  *                           top-k / nucleus truncated word distribution, in integer arithmetic that a host form repeats exactly
  *   grit_decode_step_inputs <- CaptionGenerator.get_seq_inputs in stateful mode + the word / position embedding sum
@@ -72,7 +74,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 53
+#define GRIT_ABI_VERSION 54
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -785,6 +787,38 @@ int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const
                             const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace,
                             long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
                             float* picked_logprob, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The beam-search step under constraints (no ancestor in the reference): grit_beam_step_f32 (n_maps == 1) or
+ * grit_beam_step_mean_f32 (n_maps > 1; maps is the same HOST array of device pointers) with the candidate score of every banned
+ * (beam, word) pair replaced by -inf.  Step t chooses word position t; history [B * cur_beam, t] int64 (row stride history_ld
+ * elements; may be NULL when t == 0) holds the words h_0 .. h_{t-1} of every source beam.  A beam is live when first_step != 0 or
+ * seq_mask * (prev_words != eos) != 0.  The banned set of a LIVE beam is the union of
+ *     ban_eos != 0          eos                                    (the caller sets it while t < its minimum length)
+ *     suppress[0 .. n_suppress)  always; a HOST array of ids in [0, V), copied into the kernel arguments (nothing to upload,
+ *                           nothing that a captured HIP graph has to keep alive)
+ *     no_repeat_word != 0   h_{t-1}, when t >= 1
+ *     no_repeat_ngram = n >= 1   h_{i+n-1} for every 0 <= i <= t - n with h_i .. h_{i+n-2} == h_{t-n+1} .. h_{t-1}
+ *                           (n == 1: every word of the history; nothing while t < n); 0 = off
+ * and a finished beam has none (it lives through word 0 alone).  History words outside [0, V) ban nothing and are never used as
+ * an index (they still take part in the comparisons).  A banned candidate stays a candidate with its own index: with a small V and
+ * many bans -inf candidates are selected, by ascending beam * V + word.  picked_logprob is the word's log-prob as stored, banned or
+ * not.  With every constraint off the outputs equal those of grit_beam_step_f32 / grit_beam_step_mean_f32 bit for bit; the host
+ * form is grit_amd/ops/beam.py: banned_words_host.  Outputs, workspace (grit_beam_step_workspace), limits and the order of ties
+ * are those of grit_beam_step_f32.  Further limits (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form):
+ * 0 <= t <= GRIT_BEAM_MAX_HISTORY, n_suppress <= GRIT_BEAM_MAX_SUPPRESS, and a vocabulary slice (V / 8 at the first step, else
+ * V / 2, rounded up to a multiple of 4) of at most GRIT_BEAM_MAX_SLICE words.  A suppress id outside [0, V), eos outside [0, V)
+ * with ban_eos, negative t / no_repeat_ngram, or history == NULL with t > 0: GRIT_ERR_BAD_ARG.  Two launches, no atomics on
+ * global memory, no host state; safe to capture in a HIP graph.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_BEAM_MAX_HISTORY 64
+#define GRIT_BEAM_MAX_SUPPRESS 16
+#define GRIT_BEAM_MAX_SLICE 65536
+int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                           const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                           const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos,
+                           const int* suppress, int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam,
+                           int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * One step of sampled decoding after the decoder (no ancestor in the reference, whose only decoder is beam search): one word per

@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from grit_amd.config import default_config
+from grit_amd.config import beam_constraints, default_config
 from grit_amd.tuning import load_tuned_gemms
 from models.caption import Transformer
 from models.caption.detector import build_detector
@@ -49,7 +49,7 @@ def caption_tokens(model, image, config, beam_size=None):
     device = next(model.parameters()).device
     images = nested_tensor_from_tensor_list([image]).to(device)
     return model(images, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
-                 beam_size=beam_size or config.model.beam_size, out_size=1, return_probs=False)
+                 beam_size=beam_size or config.model.beam_size, out_size=1, return_probs=False, **beam_constraints(config))
 
 
 @torch.inference_mode()
@@ -75,7 +75,7 @@ def caption_stream(model, batches, config, beam_size=None):
     if device.type != 'cuda':
         for samples in batches:
             yield model(samples, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
-                        beam_size=beam, out_size=1, return_probs=False)
+                        beam_size=beam, out_size=1, return_probs=False, **beam_constraints(config))
         return
     # The tuned GEMM table (grit_amd/tuning.py) is switched off while two streams issue library GEMMs side by side: with it, the
     # detector stream stalls for tens of ms every few batches next to the replayed decode graph (63-91 ms per batch instead of 51,
@@ -104,7 +104,8 @@ def _caption_stream_device(model, batches, config, beam, device):
                 for v in _feature_tensors(vis):
                     v.record_stream(dec_stream)
                 out = model(vis, seq=None, use_beam_search=True, max_len=config.model.beam_len,
-                            eos_idx=config.model.eos_idx, beam_size=beam, out_size=1, return_probs=False)
+                            eos_idx=config.model.eos_idx, beam_size=beam, out_size=1, return_probs=False,
+                            **beam_constraints(config))
                 done = torch.cuda.Event()
                 done.record(dec_stream)
         finally:
@@ -169,13 +170,20 @@ def run_main():
     ap.add_argument('--checkpoint', nargs='+', default=[''], help="one checkpoint, or several for an ensemble")
     ap.add_argument('--vocab', default=os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'vocab.json'))
     ap.add_argument('--beam', type=int, default=None)
+    ap.add_argument('--min-len', type=int, default=0, help="at least this many words before <eos>")
+    ap.add_argument('--no-repeat-ngram', type=int, default=0, metavar='N', help="no n-gram of N words twice in a caption (0: off)")
+    ap.add_argument('--no-repeat-word', action='store_true', help="no word twice in a row")
+    ap.add_argument('--suppress', type=int, nargs='*', default=[], metavar='ID', help="vocabulary ids that are never chosen")
+    ap.add_argument('--length-penalty', type=float, default=0.0, help="rank the final beams by score / length^this (0: off)")
     ap.add_argument('--sample', type=int, default=0, metavar='N', help="print N sampled captions instead of the best beam")
     ap.add_argument('--temperature', type=float, default=1.0)
     ap.add_argument('--top-k', type=int, default=0, help="sample among the k most probable words only (0: all)")
     ap.add_argument('--top-p', type=float, default=1.0, help="sample inside the smallest nucleus of this mass")
     ap.add_argument('--seed', type=int, default=None, help="sampling seed (default: torch's device generator)")
     a = ap.parse_args()
-    config = default_config()
+    config = default_config(**{'model.beam_min_len': a.min_len, 'model.beam_no_repeat_ngram': a.no_repeat_ngram,
+                               'model.beam_no_repeat_word': a.no_repeat_word, 'model.beam_suppress': list(a.suppress),
+                               'model.beam_length_penalty': a.length_penalty})
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
     model = build_captioner(config, device, a.checkpoint)
     if a.img.endswith('.npy'):
