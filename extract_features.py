@@ -14,13 +14,14 @@ grit_amd/datasets/caption/feature_store.py).  Differences from the reference, no
 import argparse
 import os
 
-import numpy as np
 import torch
 import torch.distributed as dist
 
 from grit_amd.config import default_config
 from grit_amd.datasets.caption.feature_store import FeatureStore
+from grit_amd.datasets.caption.field import decode_image
 from grit_amd.datasets.caption.transforms import collate_images, get_transform
+from grit_amd.ops import jpeg
 
 
 def canvas_size(transform_cfg):
@@ -46,7 +47,8 @@ def grid_tokens(H, W):
 class ImageFolder(object):
     """Every image file under `root`, id = the number after the last underscore of the file name (COCO naming)."""
 
-    def __init__(self, root):
+    def __init__(self, root, decode='host'):
+        self.decode = decode  # 'device': baseline JPEGs leave here as probed EncodedJpeg items (grit_amd/ops/jpeg.py)
         names = sorted(n for n in os.listdir(root) if n.lower().endswith(('.jpg', '.jpeg', '.png')))
         self.root, self.names = root, names
         self.img_ids = [int(n.split('_')[-1].split('.')[0]) for n in names]
@@ -55,13 +57,18 @@ class ImageFolder(object):
         return len(self.names)
 
     def __getitem__(self, i):
-        from PIL import Image
-        return np.asarray(Image.open(os.path.join(self.root, self.names[i])).convert('RGB'))
+        path = os.path.join(self.root, self.names[i])
+        if self.decode == 'device':  # probed only: the batch's entropy decode runs in decode_batch's thread pool
+            item = jpeg.probe(path)
+            if item is not None:
+                return item
+        return decode_image(path)
 
 
 @torch.inference_mode()
 def extract_vis_features(detector, images, image_ids, config, out_path, device='cuda', rank=0, world_size=1, batch_size=64):
-    """images: indexable of decoded RGB uint8 arrays [h, w, 3]; image_ids: their ids.  Returns the FeatureStore."""
+    """images: indexable of decoded RGB uint8 arrays [h, w, 3] (or EncodedJpeg, see ImageFolder); image_ids: their ids.
+    Returns the FeatureStore."""
     detector = detector.eval()
     policy = get_transform(config.dataset.transform_cfg)['valid']
     H, W = canvas_size(config.dataset.transform_cfg)
@@ -94,6 +101,8 @@ def main():
     ap.add_argument('--out', required=True)
     ap.add_argument('--checkpoint', default='')
     ap.add_argument('--batch-size', type=int, default=64)
+    ap.add_argument('--decode', choices=('host', 'device'), default=None,
+                    help="device: baseline JPEG files are reconstructed on the GPU (default: config.decode, else host)")
     a = ap.parse_args()
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', 0)))
@@ -103,7 +112,7 @@ def main():
     config.dataset.transform_cfg.randaug = False
     from inference_caption import build_model
     model = build_model(config, 'cuda', a.checkpoint)
-    data = ImageFolder(a.img_root)
+    data = ImageFolder(a.img_root, a.decode or getattr(config, 'decode', 'host'))
     store = extract_vis_features(model.detector, data, data.img_ids, config, a.out, 'cuda', rank, world, a.batch_size)
     if rank == 0:
         print('wrote', {k: tuple(v.shape) for k, v in store.arrays.items()}, 'to', a.out)

@@ -30,6 +30,8 @@ import numpy as np
 import torch
 
 from grit_amd import lib as _lib
+from grit_amd.ops.jpeg import EncodedJpeg, decode_batch
+from grit_amd.ops.staging import Staging as _Staging
 
 MEAN = (0.485, 0.456, 0.406)  # transforms/__init__.py:6-7
 STD = (0.229, 0.224, 0.225)
@@ -83,35 +85,12 @@ def _lut(mean, std, device):
     return v[None, :].sub(m).div(s).contiguous().to(device)  # Normalize
 
 
-class _Staging(object):
-    """Grow-only pinned buffers handed out round-robin; a slot is reused only after the upload that read it finished."""
-
-    def __init__(self, slots=3):
-        self.slots = [[None, None] for _ in range(slots)]  # (pinned uint8 buffer, event of its last upload)
-        self.turn = 0
-
-    def take(self, nbytes):
-        slot = self.slots[self.turn]
-        self.turn = (self.turn + 1) % len(self.slots)
-        if slot[1] is not None:
-            slot[1].synchronize()
-        if slot[0] is None or slot[0].numel() < nbytes:
-            with torch.inference_mode(False):  # the buffer outlives the caller's inference_mode block
-                slot[0] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        return slot
-
-    def upload(self, slot, nbytes, device):
-        dev = slot[0][:nbytes].to(device, non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record()
-        return dev
-
-
 _pixels_staging, _tables_staging = _Staging(), _Staging()
 
 
 def _as_u8(img):
+    if isinstance(img, EncodedJpeg):  # decoded by the device, straight into the source blob (_upload_pixels)
+        return img
     if isinstance(img, torch.Tensor):
         t = img
     else:
@@ -242,6 +221,14 @@ def plan_augment(sizes, plans, table_base=0):
 
 def _upload_pixels(imgs, offsets, src_bytes, device):
     """The packed source blob on the device, GRIT_IMAGE_SRC_PAD readable bytes behind the last image."""
+    encoded = [k for k, im in enumerate(imgs) if isinstance(im, EncodedJpeg)]
+    if encoded:  # one reconstruction for all of them, written where the resize reads; decoded entries are copied next to them
+        src = torch.empty(src_bytes + SRC_PAD, dtype=torch.uint8, device=device)
+        decode_batch([imgs[k] for k in encoded], device, out=src, offsets=[offsets[k] for k in encoded])
+        for im, off in zip(imgs, offsets):
+            if not isinstance(im, EncodedJpeg):
+                src[off:off + im.numel()].copy_(im.reshape(-1), non_blocking=im.is_cuda or im.is_pinned())
+        return src
     if all(im.is_cuda for im in imgs):
         return torch.cat([im.reshape(-1) for im in imgs] + [torch.zeros(SRC_PAD, dtype=torch.uint8, device=device)])
     if all(im.is_cuda or im.is_pinned() for im in imgs):  # decoder wrote into pinned memory: no staging copy
@@ -273,7 +260,8 @@ def _upload_tables(device, *arrays):
 
 
 def image_batch(images, sizes, mean=MEAN, std=STD, device=None, pad_to=None, augment=None):
-    """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device); sizes: list of (oh, ow).
+    """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device) or EncodedJpeg (ops/jpeg.py: reconstructed on
+    the device by one decode_batch in front of the launches); sizes: list of (oh, ow).
     augment: None, or one RandAugment plan ((name, magnitude, negate), ...) per image (may be empty), applied to the
     resized uint8 image before ToTensor as Pillow would.
 
@@ -420,7 +408,7 @@ def plan_geo(shapes, plans, filter='bilinear'):
 
 
 def image_batch_geo(images, plans, mean=MEAN, std=STD, device=None, pad_to=None):
-    """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device); plans: per image a sequence of ('hflip',),
+    """images: list of [h, w, 3] uint8 (torch / numpy / PIL, host or device) or EncodedJpeg; plans: per image a sequence of ('hflip',),
     ('resize', oh, ow) and ('crop', top, left, h, w) in the order a PIL chain would apply them (at most two resizes; resizes
     are Pillow's BILINEAR, what torchvision.transforms.functional.resize does to a PIL image).
 

@@ -62,7 +62,10 @@
  *                           cider.compute_score) and datasets/caption/metrics/cider/cider_scorer.py (counts2vec, sim, compute_cider)
  *   grit_caption_scores  <- the evaluation's scores, engine/caption_engine.py:165-190 (decode, itertools.groupby, PTBTokenizer.tokenize,
  *                           compute_scores) and datasets/caption/metrics/{bleu/bleu_scorer.py, rouge/rouge.py, cider/cider_scorer.py}
- * (none of the last fourteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ *   grit_jpeg_probe, grit_jpeg_entropy, grit_jpeg_reconstruct
+ *                        <- PIL's Image.open(path).convert('RGB') in the dataset workers (datasets/caption/field.py:65,
+ *                           tools/extract_features.py:42): libjpeg-turbo's baseline decode at its defaults
+ * (none of the last fifteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
  *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
@@ -74,7 +77,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 54
+#define GRIT_ABI_VERSION 55
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -1118,6 +1121,65 @@ int grit_det_topk_f32(const float* logits, const float* boxes, const float* size
 int grit_det_eval_img(const float* scores, const int64_t* labels, const float* boxes, const int32_t* slot, int B, int N,
                       const grit_det_gt* gt, const double* iou_thr, int T, const double* area_rng, int A, uint32_t* rec_flags,
                       int32_t* rec_rank, float* rec_score, int32_t* rec_label, uint8_t* seen, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * JPEG decoding (DESIGN "JPEG decoding"): baseline files -> the [h, w, 3] uint8 RGB pixels of libjpeg-turbo's defaults (JDCT_ISLOW,
+ * fancy upsampling; what PIL's Image.open(path).convert('RGB') returns), bit for bit.  The serial entropy stage is host code, the
+ * rest two launches for a batch.
+ *
+ * grit_jpeg_probe (host code, no GPU work): reads the markers up to the scan and fills `info`.  GRIT_ERR_UNSUPPORTED for everything
+ * outside the accepted subset -- anything but SOF0 with 8-bit samples, 8-bit quantisation tables and ONE interleaved scan of
+ * 1 component (its factors count as 1x1) or of 3 components with luma 1x1, 2x1 or 2x2 over 1x1 chroma that libjpeg takes for YCbCr (JFIF marker; else
+ * Adobe transform 1; else component ids other than 'R','G','B'); DNL; any malformed header -- the caller then decodes on the host.
+ *   info    width, height, ncomp (1: grey, 3: YCbCr); hs / vs sampling factors per component, hmax / vmax = the luma's;
+ *           mcu_cols, mcu_rows; block_cols / block_rows per component = mcu_cols * hs, mcu_rows * vs (padded to whole MCUs);
+ *           restart_interval in MCUs (0: none); scan_offset = byte offset of the first entropy-coded byte;
+ *           coef_bytes = 128 bytes per block, plane_bytes = 64 bytes per block over all components;
+ *           quant [component][64]: the component's quantisation table in natural (row-major) order
+ * grit_jpeg_entropy (host code): the Huffman decode of the scan into coef (coef_bytes >= info->coef_bytes): per component one
+ *   plane [block_rows][block_cols][64] int16, de-zigzagged, not dequantised, the planes back to back.  info: the probe's record of
+ *   the same bytes (GRIT_ERR_BAD_ARG if it is not) or NULL.  GRIT_ERR_UNSUPPORTED -- decode on the host -- for a bad Huffman table,
+ *   a code that does not exist, a run past the block, a wrong or missing restart marker, data that ends early or does not end in EOI,
+ *   a quantisation entry of 0 or more than GRIT_JPEG_MAX_PIXELS pixels (PIL's MAX_IMAGE_PIXELS: its own guard then decides; probe),
+ *   and any coefficient with |coefficient * quant| > GRIT_JPEG_COEF_BOUND (no encoder makes one from 8-bit samples; the bound keeps
+ *   the first IDCT pass inside 32 bits).  Both functions are re-entrant, allocate nothing and never read past data + nbytes.
+ *
+ * grit_jpeg_reconstruct (two launches, no atomics): jobs [n_images] grit_jpeg_job (device memory), every offset relative to the
+ * base pointer of its buffer:
+ *     coef_off   int16 ELEMENT offset of each component's coefficient plane in coef (a multiple of 8: rows load as 16 bytes)
+ *     plane_off  byte offset (a multiple of 8) of each component's sample plane in planes: block_rows * 8 rows of block_cols * 8
+ *     out_off    byte offset of the image's [height, width, 3] pixels in out (any; 4-byte aligned offsets store whole dwords)
+ *     width, height, ncomp, hmax, vmax, block_cols, block_rows, quant: as in grit_jpeg_info
+ *   PRECONDITION: every |coefficient * quant| <= GRIT_JPEG_COEF_BOUND, as grit_jpeg_entropy guarantees; the first IDCT pass works
+ *   in int32 and larger products overflow it (undefined values, no fault).  An image with ncomp = 0 (or no pixels) is skipped.
+ *   launch 1: dequantise, jidctint.c's jpeg_idct_islow, range limit: every block of every component -> planes
+ *   launch 2: per pixel Y, jdsample.c's fancy h2v1 / h2v2 chroma upsampling (replication when the chroma plane is <= 2 wide),
+ *             jdcolor.c's YCbCr -> RGB; grey images copy Y to the three channels
+ *   coef, planes 16-byte aligned; out 4-byte aligned.  max_blocks = the largest block_cols * block_rows of a component, max_pixels
+ *   = the largest width * height; n_images * 3 <= 65535.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_JPEG_COEF_BOUND 8191
+#define GRIT_JPEG_MAX_PIXELS 89478485
+typedef struct {
+    int width, height, ncomp, hmax, vmax;
+    int hs[3], vs[3];
+    int mcu_cols, mcu_rows;
+    int block_cols[3], block_rows[3];
+    int restart_interval;
+    long scan_offset, coef_bytes, plane_bytes;
+    int quant[192];
+} grit_jpeg_info;
+typedef struct {
+    long coef_off[3], plane_off[3], out_off;
+    int width, height, ncomp, hmax, vmax;
+    int block_cols[3], block_rows[3];
+    int quant[192];
+} grit_jpeg_job;
+int grit_jpeg_probe(const uint8_t* data, long nbytes, grit_jpeg_info* info);
+int grit_jpeg_entropy(const uint8_t* data, long nbytes, const grit_jpeg_info* info, void* coef, long coef_bytes);
+long grit_jpeg_planes_bytes(const grit_jpeg_info* info);
+int grit_jpeg_reconstruct(const grit_jpeg_job* jobs, int n_images, int max_blocks, long max_pixels, const void* coef, uint8_t* planes,
+                          uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }
