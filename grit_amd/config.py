@@ -44,6 +44,9 @@ _DEFAULTS = {
         # beam_min_len words before <eos>, no n-gram of beam_no_repeat_ngram words twice, no word twice in a row, vocabulary ids that
         # are never chosen, final ranking by score / length^beam_length_penalty.  Self-critical training decodes unconstrained.
         beam_min_len=0, beam_no_repeat_ngram=0, beam_no_repeat_word=False, beam_suppress=[], beam_length_penalty=0.0,
+        # diverse beam search of evaluation and inference: beam_groups groups of beam_size / beam_groups beams searched in turn, a
+        # group paying beam_diversity per earlier choice of the same word at a step (1 group: the plain search, as in the reference)
+        beam_groups=1, beam_diversity=0.0,
         dropout=0.2, attn_dropout=0.2, vocab_size=10201, max_len=54, pad_idx=1, bos_idx=2, eos_idx=3, d_model=512,
         n_heads=8, grid_net=dict(n_memories=1, n_layers=3), cap_generator=dict(decoder_name='parallel', n_layers=3),
         detector=dict(checkpoint='', d_model=512, dim_feedforward=1024, num_heads=8, num_layers=6, num_levels=4,
@@ -69,6 +72,13 @@ def beam_constraints(config):
     return dict(min_len=getattr(m, 'beam_min_len', 0), no_repeat_ngram=getattr(m, 'beam_no_repeat_ngram', 0),
                 no_repeat_word=getattr(m, 'beam_no_repeat_word', False), suppress=tuple(getattr(m, 'beam_suppress', None) or ()),
                 length_penalty=getattr(m, 'beam_length_penalty', 0.0))
+
+
+def beam_groups(config):
+    """The model.beam_groups / model.beam_diversity keys as keyword arguments of Transformer.forward / Ensemble.forward; a config
+    written before they existed gives the defaults (one group: the plain search)."""
+    m = config.model
+    return dict(num_groups=getattr(m, 'beam_groups', 1), diversity=getattr(m, 'beam_diversity', 0.0))
 
 
 def default_config(**overrides):

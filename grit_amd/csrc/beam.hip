@@ -335,6 +335,87 @@ void beam_merge(Src logp, long ld, const float* __restrict__ seq_mask, const int
     }
 }
 
+// Stage 2 of the diverse step (grit_beam_step_div_f32): the groups of a step are resolved one after the other on the <= 128
+// candidates that stage 1 left, one wave per image.  A group pays `diversity` per earlier selection of the same word in this step,
+// and the penalty only lowers candidates -- in one source row at most |P| <= k - g of them, P being the words picked so far -- so
+// the g best penalised candidates of a row are among its k best unpenalised ones, which is what stage 1 kept (ties included: a
+// candidate outside them has k better ones, of which g stay unpenalised and so stay better).  Only the candidates that the penalty
+// touches (word in P, live row, finite score) are scored again, from the source and the running score, so the mean of an ensemble
+// is formed as in stage 1; all the others keep stage 1's value, which is the penalised one for a count of 0.  The picks of the
+// step sit in registers at their output position (-1: picked from a finished row, which counts nothing).
+template <class Src>
+__global__ __launch_bounds__(64)
+void beam_merge_groups(Src logp, long ld, const float* __restrict__ seq_lp, const float* __restrict__ seq_mask,
+                       const int64_t* __restrict__ prev_words, int eos, int first_step, int cur, int V, int k, int parts, int G,
+                       float diversity, const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
+                       int64_t* __restrict__ sel_beam, int64_t* __restrict__ sel_word, float* __restrict__ new_lp,
+                       float* __restrict__ new_mask, float* __restrict__ picked) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int lists = cur * parts, n = lists * k, g = k / G;  // <= 128 candidates, two per lane
+    constexpr int kNone = 0x7fffffff;
+    auto alive_of = [&](int row_id) {
+        return first_step ? 1.f : seq_mask[row_id] * (prev_words[row_id] != (int64_t)eos ? 1.f : 0.f);
+    };
+    float v[2]; int i[2], row[2], word[2]; bool live[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int c = lane + 64 * h;
+        v[h] = -INFINITY; i[h] = kNone; row[h] = -1; word[h] = -1; live[h] = false;
+        if (c < n) {
+            const int l = c / k, r = c - l * k;
+            v[h] = ws_val[((size_t)b * lists + l) * kMaxK + r];
+            i[h] = ws_idx[((size_t)b * lists + l) * kMaxK + r];
+            if (i[h] != kNone) {  // a slice shorter than k leaves empty entries
+                row[h] = i[h] / V; word[h] = i[h] - row[h] * V;
+                live[h] = alive_of(b * cur + row[h]) != 0.f;
+            }
+        }
+    }
+    int pw[kMaxK];
+#pragma unroll
+    for (int q = 0; q < kMaxK; ++q) pw[q] = -1;
+    for (int grp = 0; grp < G; ++grp) {
+        const int done = grp * g;                                // the picks of the earlier groups
+        const int r0 = cur == 1 ? 0 : done, r1 = cur == 1 ? 1 : done + g;  // this group's source rows
+        float pv[2]; int pi[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const bool mine = row[h] >= r0 && row[h] < r1;
+            pv[h] = mine ? v[h] : -INFINITY; pi[h] = mine ? i[h] : kNone;
+            if (mine && live[h]) {
+                int count = 0;
+#pragma unroll
+                for (int q = 0; q < kMaxK; ++q) count += (q < done && pw[q] == word[h]) ? 1 : 0;
+                if (count > 0 && v[h] > -INFINITY && v[h] < INFINITY) {
+                    const size_t row_id = (size_t)(b * cur + row[h]);
+                    pv[h] = __fadd_rn(seq_lp[row_id], __fsub_rn(logp.at(row_id * ld + word[h]), __fmul_rn(diversity, (float)count)));
+                }
+            }
+        }
+        for (int r = 0; r < g; ++r) {
+            const bool second = better(pv[1], pi[1], pv[0], pi[0]);
+            float bvv = second ? pv[1] : pv[0]; int bii = second ? pi[1] : pi[0], o = lane * 2 + (second ? 1 : 0);
+            wave_best(bvv, bii, o);
+            if (o == lane * 2) { pv[0] = -INFINITY; pi[0] = kNone; }
+            if (o == lane * 2 + 1) { pv[1] = -INFINITY; pi[1] = kNone; }
+            int jb = r0, w = 0;  // (fewer than g candidates cannot happen with V >= k; never index with an empty entry)
+            if (bii != kNone) { jb = bii / V; w = bii - jb * V; }
+            const int row_id = b * cur + jb;
+            const float alive = alive_of(row_id);
+            const int pos = done + r;
+#pragma unroll
+            for (int q = 0; q < kMaxK; ++q)
+                if (q == pos) pw[q] = alive != 0.f ? w : -1;
+            if (lane == 0) {
+                const size_t at = (size_t)b * k + pos;
+                sel_beam[at] = jb; sel_word[at] = w;
+                new_lp[at] = bvv; new_mask[at] = alive;
+                picked[at] = logp.at((size_t)row_id * ld + w) * alive;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" long grit_beam_step_workspace(int B, int cur_beam, int k) {
@@ -349,7 +430,7 @@ template <class Src, class Part = Src>  // Part: what stage 1 reads, Src itself 
 int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos, int first_step,
               int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
               float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream,
-              const Bans* bans = nullptr) {
+              const Bans* bans = nullptr, int groups = 0 /* 0: the plain merge */, float diversity = 0.f) {
     if (!seq_logprob || !workspace || !sel_beam || !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob ||
         B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V)
         return GRIT_ERR_BAD_ARG;
@@ -374,8 +455,14 @@ int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask,
     else
         hipLaunchKernelGGL((beam_partial<kMaxK, Part>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part, ld,
                            seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    hipLaunchKernelGGL(beam_merge<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_mask, prev_words, eos, first_step,
-                       cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob);
+    if (groups > 0)
+        hipLaunchKernelGGL(beam_merge_groups<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_logprob, seq_mask,
+                           prev_words, eos, first_step, cur_beam, V, k, parts, groups, diversity, ws_val, ws_idx, sel_beam, sel_word,
+                           new_seq_logprob, new_seq_mask, picked_logprob);
+    else
+        hipLaunchKernelGGL(beam_merge<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_mask, prev_words, eos,
+                           first_step, cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
+                           picked_logprob);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }
 
@@ -411,41 +498,77 @@ extern "C" int grit_beam_step_mean_f32(const float* const* maps, int n_maps, lon
                      sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
 }
 
+namespace {
+
+// The entry points with rules: the constrained step (groups == 0: the plain merge) and the diverse step.  `con`: stage 1 applies
+// the bans; without it the constraint arguments are not read.
+int beam_step_rules(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                    const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, bool con,
+                    const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos,
+                    const int* suppress, int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
+                    float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream, int groups, float diversity) {
+    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0) return GRIT_ERR_BAD_ARG;
+    if (con && (t < 0 || no_repeat_ngram < 0 || n_suppress < 0 || (n_suppress > 0 && !suppress) ||
+                (t > 0 && (!history || history_ld < t)) || (ban_eos && (eos < 0 || eos >= V))))
+        return GRIT_ERR_BAD_ARG;
+    if (n_maps > kMaxMaps || (con && (t > kMaxHistory || n_suppress > kMaxSuppress))) return GRIT_ERR_UNSUPPORTED;
+    Bans bans{};
+    if (con) {
+        bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
+        bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
+        bans.n_sup = n_suppress;
+        for (int i = 0; i < n_suppress; ++i) {
+            if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
+            bans.sup[i] = suppress[i];
+        }
+    }
+    MeanMaps mean{};
+    for (int m = 0; m < n_maps; ++m) {
+        if (!maps[m]) return GRIT_ERR_BAD_ARG;
+        mean.t.p[m] = maps[m];
+    }
+    mean.n = n_maps;
+    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
+    mean.factor = (float)outputs / (float)(outputs * n_maps);
+    auto run = [&](auto src) {
+        using Src = decltype(src);
+        if (con)
+            return beam_step<Src, Banned<Src>>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
+                                               workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob,
+                                               stream, &bans, groups, diversity);
+        return beam_step<Src, Src>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
+                                   workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, nullptr,
+                                   groups, diversity);
+    };
+    return n_maps == 1 ? run(OneMap{maps[0]}) : run(mean);
+}
+
+}  // namespace
+
 extern "C" int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
                                       const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
                                       const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
                                       int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
                                       int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
                                       float* picked_logprob, void* stream) {
-    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0 || t < 0 || no_repeat_ngram < 0 || n_suppress < 0 ||
-        (n_suppress > 0 && !suppress) || (t > 0 && (!history || history_ld < t)) || (ban_eos && (eos < 0 || eos >= V)))
-        return GRIT_ERR_BAD_ARG;
-    if (n_maps > kMaxMaps || t > kMaxHistory || n_suppress > kMaxSuppress) return GRIT_ERR_UNSUPPORTED;
-    Bans bans{};
-    bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
-    bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
-    bans.n_sup = n_suppress;
-    for (int i = 0; i < n_suppress; ++i) {
-        if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
-        bans.sup[i] = suppress[i];
-    }
-    if (n_maps == 1) {
-        if (!maps[0]) return GRIT_ERR_BAD_ARG;
-        return beam_step<OneMap, Banned<OneMap>>(OneMap{maps[0]}, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam,
-                                                 V, k, workspace, workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
-                                                 picked_logprob, stream, &bans);
-    }
-    MeanMaps src{};
-    for (int m = 0; m < n_maps; ++m) {
-        if (!maps[m]) return GRIT_ERR_BAD_ARG;
-        src.t.p[m] = maps[m];
-    }
-    src.n = n_maps;
-    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
-    src.factor = (float)outputs / (float)(outputs * n_maps);
-    return beam_step<MeanMaps, Banned<MeanMaps>>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k,
-                                                 workspace, workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
-                                                 picked_logprob, stream, &bans);
+    return beam_step_rules(maps, n_maps, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, true, history,
+                           history_ld, t, no_repeat_ngram, no_repeat_word, ban_eos, suppress, n_suppress, workspace, workspace_bytes,
+                           sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, 0, 0.f);
+}
+
+extern "C" int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                                      const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                                      int groups, float diversity, const int64_t* history, long history_ld, int t,
+                                      int no_repeat_ngram, int no_repeat_word, int ban_eos, const int* suppress, int n_suppress,
+                                      void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
+                                      float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
+    if (k <= 0 || groups < 1 || no_repeat_ngram < 0 || n_suppress < 0) return GRIT_ERR_BAD_ARG;
+    if (k > kMaxK || k % groups != 0 || (cur_beam != 1 && cur_beam != k) || V < k || !(diversity >= 0.f && diversity < INFINITY))
+        return GRIT_ERR_UNSUPPORTED;
+    const bool con = no_repeat_ngram > 0 || no_repeat_word || ban_eos || n_suppress > 0;  // all off: t and history are not read
+    return beam_step_rules(maps, n_maps, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, con, history,
+                           history_ld, t, no_repeat_ngram, no_repeat_word, ban_eos, suppress, n_suppress, workspace, workspace_bytes,
+                           sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, groups, diversity);
 }
 
 extern "C" int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t* idx_out, float* val_out, void* stream) {

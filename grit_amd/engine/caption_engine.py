@@ -20,7 +20,7 @@ import torch
 import torch.distributed as dist
 from torch.nn import NLLLoss
 
-from grit_amd.config import beam_constraints
+from grit_amd.config import beam_constraints, beam_groups
 from grit_amd.data import PAD
 from grit_amd.utils.misc import get_rank, get_world_size, is_dist_avail_and_initialized
 
@@ -297,7 +297,7 @@ def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='
         with torch.no_grad():
             out, _ = model(batch['samples'], seq=None, use_beam_search=True, max_len=config.model.beam_len,
                            eos_idx=config.model.eos_idx, beam_size=config.model.beam_size, out_size=1,
-                           return_probs=False, **beam_constraints(config))
+                           return_probs=False, **beam_constraints(config), **beam_groups(config))
         if out.is_cuda:
             torch.cuda.synchronize()
         times.append(time.time() - t0)

@@ -105,17 +105,19 @@ class Ensemble(BeamSearchSteps, nn.Module):
         length_penalty = float(kwargs.pop('length_penalty', 0.0) or 0.0)
         if length_penalty < 0:
             raise ValueError("length_penalty must be >= 0, not %g" % length_penalty)
+        # Transformer.forward's diverse search: taken out of kwargs like the rest, so that the search can still replay from a graph
+        groups = beam_ops.groups(beam_size, kwargs.pop('num_groups', 1), kwargs.pop('diversity', 0.0))
         if decode != 'beam':
             raise NotImplementedError("Ensemble only decodes by beam search: decode=%r is for a single Transformer (sampling from "
                                       "an average of distributions is not built)" % (decode,))
         self._check_placement()
         feats = self._member_features(samples)
         if self._graph_eligible(feats, return_probs, kwargs):
-            return self._beam_search_graphed(feats, max_len, eos_idx, beam_size, out_size, constraints, length_penalty)
+            return self._beam_search_graphed(feats, max_len, eos_idx, beam_size, out_size, constraints, length_penalty, groups)
         from grit_amd.ops.linear import suspend_single_use
         with suspend_single_use():
             return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
-                                           length_penalty=length_penalty, **kwargs)
+                                           length_penalty=length_penalty, groups=groups, **kwargs)
 
     def _graph_eligible(self, feats, return_probs, kwargs):
         if not _tr._GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
@@ -123,16 +125,16 @@ class Ensemble(BeamSearchSteps, nn.Module):
         _, device = self.get_bs_device(feats)
         return device.type == 'cuda' and not torch.cuda.is_current_stream_capturing()
 
-    def _beam_search_graphed(self, feats, max_len, eos_idx, beam_size, out_size, constraints=None, length_penalty=0.0):
+    def _beam_search_graphed(self, feats, max_len, eos_idx, beam_size, out_size, constraints=None, length_penalty=0.0, groups=None):
         """`Transformer._beam_search_graphed` for K members: one graph per (every member's probe-parameter storage, batch, beam,
-        length, constraints, feature shapes), least recently used of 8 dropped, warm-up on a side stream.  The members' own graph
-        caches are not touched."""
+        length, constraints, beam groups, feature shapes), least recently used of 8 dropped, warm-up on a side stream.  The
+        members' own graph caches are not touched."""
         def decode():
             return self._beam_search_eager([dict(s) for s in static_in], max_len, eos_idx, beam_size, out_size, False,
-                                           constraints=constraints, length_penalty=length_penalty)
+                                           constraints=constraints, length_penalty=length_penalty, groups=groups)
 
         names = [sorted(k for k, v in f.items() if isinstance(v, torch.Tensor)) for f in feats]
-        key = (max_len, eos_idx, beam_size, out_size, constraints, length_penalty, torch.is_inference_mode_enabled(),
+        key = (max_len, eos_idx, beam_size, out_size, constraints, length_penalty, groups, torch.is_inference_mode_enabled(),
                feats[0][names[0][0]].device.index) + \
             tuple((p.data_ptr(), p.dtype) for m in self.models for p in self._probes(m)) + \
             tuple(tuple((k, tuple(f[k].shape), f[k].dtype) for k in n) for f, n in zip(feats, names))
@@ -164,7 +166,7 @@ class Ensemble(BeamSearchSteps, nn.Module):
         return tuple(o.clone() for o in static_out)
 
     def _beam_search_eager(self, feats, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                           **kwargs):
+                           groups=None, **kwargs):
         batch_size, device = self.get_bs_device(feats)
         self.seq_mask = torch.ones((batch_size, beam_size, 1), device=device)      # 1 while the beam is alive
         self.seq_logprob = torch.zeros((batch_size, 1, 1), device=device)          # running score per beam
@@ -179,31 +181,36 @@ class Ensemble(BeamSearchSteps, nn.Module):
             for t in range(max_len):
                 feats, outputs = self.iter(timestep=t, samples=feats, outputs=outputs, return_probs=return_probs,
                                            batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, constraints=constraints,
-                                           **kwargs)
+                                           groups=groups, **kwargs)
         return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty)
 
     def step(self, timestep, prev_output, samples, seq, mode='teacher_forcing', **kwargs):
         """Every member's word log-probabilities for this step (samples: one feature dict per member), [B * cur_beam, 1, V] each."""
         return [m.step(timestep, prev_output, f, seq, mode=mode, **kwargs) for m, f in zip(self.models, samples)]
 
-    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, **kwargs):
+    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, groups=None,
+             **kwargs):
         cur_beam = 1 if timestep == 0 else beam_size
         maps = [lp.view(batch_size, cur_beam, -1)
                 for lp in self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)]
         fused, word_logprob = None, None
         if constraints is not None:
             outputs = self._history(outputs)
-        if _tr._FUSED_BEAM_STEP and not return_probs and not kwargs and beam_ops.supported_mean(maps, cur_beam, beam_size):
+        on_device = beam_ops.supported_mean(maps, cur_beam, beam_size) if groups is None else \
+            beam_ops.supported_div(maps, cur_beam, beam_size, groups.num_groups)
+        if _tr._FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if constraints is None:
+            if groups is not None:  # None beyond the kernel's limits, here and below: the composed form
+                fused = beam_ops.beam_step_div(maps, *state, *groups, outputs[0] if outputs else None, timestep, constraints)
+            elif constraints is None:
                 fused = beam_ops.beam_step_mean(maps, *state)
-            else:  # None beyond the kernel's limits: the composed form
+            else:
                 fused = beam_ops.beam_step_con(maps, *state, outputs[0] if outputs else None, timestep, constraints)
         if fused is None:
             word_logprob = torch.mean(torch.stack(maps), 0)
         outputs = self._beam_advance(self.models, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
-                                     eos_idx, constraints=constraints, **kwargs)
+                                     eos_idx, constraints=constraints, groups=groups, **kwargs)
         return samples, outputs
 
 

@@ -89,11 +89,18 @@ class BeamSearchSteps(object):
         return fn
 
     def _beam_advance(self, members, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size, eos_idx,
-                      constraints=None, **kwargs):
+                      constraints=None, groups=None, **kwargs):
         """The body of `iter` after the word log-probabilities word_logprob [B, cur_beam, V]: `fused` holds what the fused step
         returned (sel_beam, sel_word, seq_logprob, seq_mask, picked), or is None for the composed torch form.  `constraints`
-        (ops/beam.py) bans words per live beam; `outputs` then holds the history as one tensor (`_history`)."""
+        (ops/beam.py) bans words per live beam; `outputs` then holds the history as one tensor (`_history`).  `groups`
+        (ops/beam.py: Groups) makes it the step of a diverse search, whose composed form is beam_step_groups_host."""
         cur_beam = 1 if timestep == 0 else beam_size
+        if fused is None and groups is not None:
+            state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None)
+            fused = beam_ops.beam_step_groups_host(word_logprob, *state, eos_idx, beam_size, *groups,
+                                                   outputs[0] if outputs else None, timestep, constraints)
+            if return_probs and timestep > 0:  # the plain composed form records the maps of finished beams as zeros
+                word_logprob = word_logprob * (self.seq_mask * (self.selected_words.view(batch_size, cur_beam, 1) != eos_idx).float())
         if fused is not None:
             selected_beam, selected_words, seq_logprob, seq_mask, picked = fused
         else:
@@ -195,10 +202,12 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
 
     def forward(self, images, seq, use_beam_search=False, max_len=20, eos_idx=3, beam_size=5, out_size=1,
                 return_probs=False, decode='beam', temperature=1.0, top_k=0, top_p=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                no_repeat_word=False, suppress=(), length_penalty=0.0, **kwargs):
+                no_repeat_word=False, suppress=(), length_penalty=0.0, num_groups=1, diversity=0.0, **kwargs):
         """Beam search under constraints (ops/beam.py): at least `min_len` words before <eos>, no n-gram of `no_repeat_ngram`
         words twice, no word twice in a row (`no_repeat_word`), the ids of `suppress` never; `length_penalty` = alpha ranks the
         final hypotheses by score / length^alpha.  All off by default.
+        Diverse beam search: `num_groups` groups of beam_size / num_groups beams are searched in turn at every step, and a group
+        pays `diversity` for every time a word was already chosen at this step by an earlier group; one group is the plain search.
         decode='sample' (with use_beam_search=True): `beam_size` independent samples per image from the word distribution at
         `temperature`, truncated to the `top_k` most probable words (0: all) and to the nucleus of mass `top_p`; `seed` is an
         integer, or None for a seed from torch's device generator.  Returns tokens and log-probs [B, out_size, max_len]."""
@@ -208,20 +217,23 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         length_penalty = float(length_penalty or 0.0)
         if length_penalty < 0:
             raise ValueError("length_penalty must be >= 0, not %g" % length_penalty)
+        groups = beam_ops.groups(beam_size, num_groups, diversity)
         if decode == 'sample':
             if constraints is not None or length_penalty != 0:
                 raise NotImplementedError("decode='sample' takes no beam-search constraints and no length penalty")
+            if groups is not None:
+                raise NotImplementedError("decode='sample' draws independent samples: beam groups are for decode='beam'")
             if return_probs or kwargs:
                 raise NotImplementedError("decode='sample' returns the sampled words' log-probs only and takes no further arguments")
             return self.sample_decode(images, max_len, eos_idx, beam_size, out_size, temperature, top_k, top_p, seed)
         if decode != 'beam':
             raise ValueError("decode must be 'beam' or 'sample', not %r" % (decode,))
         return self.beam_search(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
-                                length_penalty=length_penalty, **kwargs)
+                                length_penalty=length_penalty, groups=groups, **kwargs)
 
     # ------------------------------------------------------------------ beam search
     def beam_search(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                    **kwargs):
+                    groups=None, **kwargs):
         """Inference on a HIP device (no autograd, eval mode): the decode loop -- grid net + `max_len` decoder steps + beam
         bookkeeping, ~5 000 small kernels whose launches bound the loop at ~2.7 ms of host time per step -- is captured ONCE per
         (batch, beam, length, feature shapes) into a HIP graph and replayed from then on (next-row N1: the device-side beam
@@ -230,11 +242,11 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         if self._graph_eligible(images, return_probs, kwargs):
             vis = images if self.cached_features else self.detector(images)
             return self._beam_search_graphed(dict(vis), max_len, eos_idx, beam_size, out_size, constraints=constraints,
-                                             length_penalty=length_penalty)
+                                             length_penalty=length_penalty, groups=groups)
         from grit_amd.ops.linear import suspend_single_use
         with suspend_single_use():  # with gradient (self-critical training) the decoder's weights are used once per STEP
             return self._beam_search_eager(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
-                                           length_penalty=length_penalty, **kwargs)
+                                           length_penalty=length_penalty, groups=groups, **kwargs)
 
     def _graph_eligible(self, images, return_probs, kwargs):
         if not _GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
@@ -251,14 +263,14 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
             self.cached_features = was
 
     def _beam_search_graphed(self, vis, max_len, eos_idx, beam_size, out_size, sampling=None, seed=None, constraints=None,
-                             length_penalty=0.0):
+                             length_penalty=0.0, groups=None):
         """sampling = (temperature, top_k, top_p) captures the sampled decode instead: part of the key, with the seed in a static
-        device tensor that is rewritten from `seed` (a one-element device tensor) before every replay.  The constraint tuple and
-        the length penalty of a beam search are part of the key as well: they are baked into the captured launches."""
+        device tensor that is rewritten from `seed` (a one-element device tensor) before every replay.  The constraint tuple, the
+        length penalty and the beam groups of a beam search are part of the key as well: they are baked into the captured launches."""
         def decode(feats, static_seed):
             if sampling is None:
                 return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, False, constraints=constraints,
-                                               length_penalty=length_penalty)
+                                               length_penalty=length_penalty, groups=groups)
             return self._sample_eager(feats, max_len, eos_idx, beam_size, out_size, *sampling, static_seed)
 
         names = sorted(k for k, v in vis.items() if isinstance(v, torch.Tensor))
@@ -266,8 +278,8 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         # in-place writers -- optimizer steps, load_state_dict -- need no invalidation.  What does: parameter STORAGE being
         # replaced (module.to(dtype), Bf16Compute wrapping): the addresses of the first and last decoder parameters are in the key.
         probe = (self.grid_net.fc.weight, self.cap_generator.fc.weight)
-        key = (max_len, eos_idx, beam_size, out_size, sampling, constraints, length_penalty, torch.is_inference_mode_enabled(),
-               vis[names[0]].device.index) + \
+        key = (max_len, eos_idx, beam_size, out_size, sampling, constraints, length_penalty, groups,
+               torch.is_inference_mode_enabled(), vis[names[0]].device.index) + \
             tuple((p.data_ptr(), p.dtype) for p in probe) + \
             tuple((k, tuple(vis[k].shape), vis[k].dtype) for k in names)
         entry = self._decode_graphs.pop(key, None)
@@ -298,7 +310,7 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         return tuple(o.clone() for o in static_out)
 
     def _beam_search_eager(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                           **kwargs):
+                           groups=None, **kwargs):
         batch_size, device = self.get_bs_device(images)
         self.seq_mask = torch.ones((batch_size, beam_size, 1), device=device)      # 1 while the beam is alive
         self.seq_logprob = torch.zeros((batch_size, 1, 1), device=device)          # running score per beam
@@ -310,7 +322,7 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
             for t in range(max_len):
                 images, outputs = self.iter(timestep=t, samples=images, outputs=outputs, return_probs=return_probs,
                                             batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, constraints=constraints,
-                                            **kwargs)
+                                            groups=groups, **kwargs)
         return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty)
 
     # ------------------------------------------------------------------ sampled decoding
@@ -405,23 +417,28 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
     def _kv_cached_modules(self):
         return [layer.self_att for layer in self.cap_generator.layers]
 
-    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, **kwargs):
+    def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, groups=None,
+             **kwargs):
         cur_beam = 1 if timestep == 0 else beam_size
         word_logprob = self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)
         word_logprob = word_logprob.view(batch_size, cur_beam, -1)
         fused = None
         if constraints is not None:
             outputs = self._history(outputs)
-        if _FUSED_BEAM_STEP and not return_probs and not kwargs and beam_ops.supported(word_logprob, cur_beam, beam_size):
+        on_device = beam_ops.supported(word_logprob, cur_beam, beam_size) if groups is None else \
+            beam_ops.supported_div([word_logprob], cur_beam, beam_size, groups.num_groups)
+        if _FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
             # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py)
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if constraints is None:
+            if groups is not None:  # None beyond the kernel's limits, here and below: the composed form
+                fused = beam_ops.beam_step_div([word_logprob], *state, *groups, outputs[0] if outputs else None, timestep, constraints)
+            elif constraints is None:
                 fused = beam_ops.beam_step(word_logprob, *state)
-            else:  # None beyond the kernel's limits: the composed form below
+            else:
                 fused = beam_ops.beam_step_con([word_logprob], *state, outputs[0] if outputs else None, timestep, constraints)
         outputs = self._beam_advance((self,), timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
-                                     eos_idx, constraints=constraints, **kwargs)
+                                     eos_idx, constraints=constraints, groups=groups, **kwargs)
         return samples, outputs
 
     def _follow_beams(self, selected_beam, cur_beam, batch_size, beam_size):

@@ -1,7 +1,9 @@
 """One beam-search step after the decoder as two launches (grit_beam_step_f32, include/grit_hip.h): the finished-beam masking,
 candidate scores, top-k over beam x vocabulary, beam / word split and the score / mask / log-prob gathers of the reference's
 Transformer.iter (models/caption/transformer.py:208-240), bit-identical to the composed torch form.  `beam_step_mean` is the same
-step for an ensemble (models/caption/ensemble.py:128-214): the average of the members' maps (grit_beam_step_mean_f32)."""
+step for an ensemble (models/caption/ensemble.py:128-214): the average of the members' maps (grit_beam_step_mean_f32).  Past the
+reference: the step under constraints (grit_beam_step_con_f32) and the step of a diverse search over beam groups
+(grit_beam_step_div_f32), each with its host form in torch ops."""
 import collections
 import ctypes
 
@@ -206,4 +208,146 @@ def beam_step_con(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, bea
     if st == _lib.ERR_UNSUPPORTED:
         return None
     _lib.check(st, "grit_beam_step_con_f32")
+    return sel_beam, sel_word, new_lp, new_mask, picked
+
+
+# ------------------------------------------------------------------------------------------------------ beam groups
+# Diverse beam search (Vijayakumar et al. 2016, the num_beam_groups / diversity_penalty of the generation libraries): beam_size =
+# G * g, group i owns the beam rows [i * g, (i + 1) * g) for the whole search, and within a step the groups are resolved in the order
+# 0 .. G - 1 per image.  counts[w] = how many selections of the earlier groups in THIS step chose word w from a live source row
+# (a finished row that survives through word 0 chose nothing; two beams choosing w count 2).  Group i scores
+#   live row j, word w:  seq_logprob[j] + (word_logprob[j, w] - diversity * float(counts[w]))     three rounded fp32 operations
+#   finished row j:      seq_logprob[j] at word 0, -999 elsewhere; no penalty
+#   banned (j, w):       -inf
+# and takes its g best of its g * V candidates, value descending, ties by ascending row * V + word.  At the first step every group
+# reads row 0.  The running score that moves on is the PENALISED value (as the generation libraries keep it), `picked` the
+# unpenalised word log-prob.  With counts == 0 the score is the plain step's bit for bit.  `beam_step_groups_host` states this in
+# torch ops; grit_beam_step_div_f32 is the same on the device in the two launches of a step.
+Groups = collections.namedtuple("Groups", "num_groups diversity")
+
+
+def groups(beam_size, num_groups=1, diversity=0.0):
+    """The validated (num_groups, diversity) of one search (hashable: part of the decode-graph key), or None for one group, which
+    is the plain search whatever the penalty."""
+    if isinstance(num_groups, bool) or int(num_groups) != num_groups:
+        raise ValueError("num_groups must be an integer, not %r" % (num_groups,))
+    num_groups, diversity = int(num_groups), float(diversity)
+    if num_groups < 1:
+        raise ValueError("num_groups must be >= 1, not %d" % num_groups)
+    if beam_size % num_groups != 0:
+        raise ValueError("num_groups = %d does not divide beam_size = %d" % (num_groups, beam_size))
+    if not 0.0 <= diversity < float('inf'):  # refuses NaN as well
+        raise ValueError("diversity must be finite and >= 0, not %r" % diversity)
+    return None if num_groups == 1 else Groups(num_groups, diversity)
+
+
+def beam_step_groups_host(word_logprob, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, num_groups, diversity, history=None,
+                          t=0, con=None):
+    """The grouped step in torch ops, on any device and with gradient: the arguments of `beam_step` (word_logprob is the mean
+    already for an ensemble), the group count and penalty, and for a constraint tuple `con` the history [B, cur_beam, t] and the
+    step.  Returns what `beam_step` returns.  Selection is a stable descending sort, so ties resolve by index."""
+    B, cur, V = word_logprob.shape
+    g = beam_size // num_groups
+    if g * num_groups != beam_size or cur not in (1, beam_size):
+        raise ValueError("%d groups over %d beams with %d source rows" % (num_groups, beam_size, cur))
+    seq_logprob = seq_logprob.reshape(B, cur, 1)
+    if prev_words is None:
+        alive = torch.ones((B, cur, 1), dtype=torch.float32, device=word_logprob.device)
+    else:
+        alive = seq_mask.reshape(B, cur, 1) * (prev_words.reshape(B, cur, 1) != eos_idx).float()
+    live = alive != 0
+    frozen = seq_logprob.expand(B, cur, V).clone()
+    frozen[:, :, 1:] = -999  # a finished beam survives only through vocabulary index 0
+    banned = None
+    if con is not None:
+        if history is None:
+            history = torch.zeros((B, cur, 0), dtype=torch.long, device=word_logprob.device)
+        banned = banned_words_host(history, None if prev_words is None else alive, t, eos_idx, V, **con._asdict())
+    penalty = torch.tensor(float(diversity), dtype=torch.float32, device=word_logprob.device)
+    counts = torch.zeros((B, V), dtype=torch.float32, device=word_logprob.device)
+    sel_beam, sel_word, new_lp = [], [], []
+    for i in range(num_groups):
+        lo, hi = (0, 1) if cur == 1 else (i * g, (i + 1) * g)
+        cand = seq_logprob[:, lo:hi] + (word_logprob[:, lo:hi] - (penalty * counts).unsqueeze(1))
+        cand = torch.where(live[:, lo:hi], cand, frozen[:, lo:hi])
+        if banned is not None:
+            cand = cand.masked_fill(banned[:, lo:hi], float('-inf'))
+        value, index = torch.sort(cand.reshape(B, -1), dim=-1, descending=True, stable=True)
+        value, index = value[:, :g], index[:, :g]
+        local = torch.div(index, V, rounding_mode='floor')
+        word = index - local * V
+        source = local + lo
+        counts = counts.scatter_add(1, word, (torch.gather(alive[:, :, 0], 1, source) != 0).float())
+        sel_beam.append(source)
+        sel_word.append(word)
+        new_lp.append(value)
+    sel_beam, sel_word = torch.cat(sel_beam, 1), torch.cat(sel_word, 1)
+    col = sel_beam.unsqueeze(-1)
+    new_mask = torch.gather(alive, 1, col)
+    picked = torch.gather(torch.gather(word_logprob, 1, col.expand(B, beam_size, V)), 2, sel_word.unsqueeze(-1)) * new_mask
+    return sel_beam, sel_word, torch.cat(new_lp, 1).unsqueeze(-1), new_mask, picked
+
+
+def supported_div(word_logprobs, cur_beam, beam_size, num_groups):
+    """The grouped step runs on the device kernel: what `supported_mean` asks of the maps, and a vocabulary of at least beam_size
+    words (a group always finds its g candidates among stage 1's)."""
+    return (supported_mean(word_logprobs, cur_beam, beam_size) and cur_beam in (1, beam_size) and beam_size % num_groups == 0
+            and word_logprobs[0].shape[-1] >= beam_size)
+
+
+def beam_step_div(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, num_groups, diversity, history=None, t=0,
+                  con=None):
+    """The grouped step of one map or of the mean of several on the device (grit_beam_step_div_f32: two launches, nothing
+    uploaded), under the constraint tuple `con` (None: unconstrained; history and t are then not read).  Returns None when the call
+    is outside the kernel's limits (a beam above 8, fewer words than beams, and with constraints t > 64 or more than 16 suppress
+    ids or a slice above 65536 words): the caller uses `beam_step_groups_host`."""
+    B, cur, V = word_logprobs[0].shape
+    if beam_size > 8 or V < beam_size or cur not in (1, beam_size) or beam_size % num_groups != 0 or len(word_logprobs) > MAX_MAPS:
+        return None
+    if con is not None and (t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS):
+        return None
+    # the kernel reads evenly spaced rows of adjacent words (any row stride >= V); every other layout is copied
+    ld = {m.stride(0) if cur == 1 else m.stride(1) for m in word_logprobs}
+    spaced = len(ld) == 1 and min(ld) >= V and all(m.stride(2) == 1 and (cur == 1 or m.stride(0) == cur * m.stride(1))
+                                                   for m in word_logprobs)
+    maps = list(word_logprobs) if spaced else [m.contiguous() for m in word_logprobs]
+    ld = min(ld) if spaced else V
+    first = prev_words is None
+    dev = maps[0].device
+    L = _lib.load()
+    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
+    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
+    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    slp = seq_logprob.reshape(-1).float().contiguous()
+    if slp.numel() != B * cur:
+        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
+    sm = pw = hist = None
+    if not first:
+        sm = seq_mask.reshape(-1).float().contiguous()
+        pw = prev_words.reshape(-1).contiguous()
+        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
+            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
+    if con is None:
+        con, t = Constraints(0, 0, False, ()), 0
+    if t > 0:
+        hist = history.reshape(B * cur, -1)
+        if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
+            raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
+        hist = hist if hist.stride(1) == 1 else hist.contiguous()
+    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host arrays: passed by value to the kernel
+    ids = (ctypes.c_int * max(1, len(con.suppress)))(*con.suppress)
+    with _lib.device_guard(dev):
+        st = L.grit_beam_step_div_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), ld, _ptr(slp), _ptr(sm),
+                                      _ptr(pw), int(eos_idx), int(first), B, cur, V, beam_size, int(num_groups), float(diversity),
+                                      _ptr(hist), hist.stride(0) if hist is not None else 0, int(t), con.no_repeat_ngram,
+                                      int(con.no_repeat_word), int(t < con.min_len), ctypes.cast(ids, ctypes.c_void_p),
+                                      len(con.suppress), _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp),
+                                      _ptr(new_mask), _ptr(picked), _lib.current_stream_ptr())
+    if st == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(st, "grit_beam_step_div_f32")
     return sel_beam, sel_word, new_lp, new_mask, picked

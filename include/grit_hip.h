@@ -49,6 +49,8 @@
  *                           torch.mean(torch.stack(per_model), 0) followed by the body of `iter`)
  *   grit_beam_step_con_f32 <- nothing in the reference (its search cannot be steered): the same step, of one map or of the mean,
  *                           with a per-beam set of banned words applied while the candidates are scored
+ *   grit_beam_step_div_f32 <- nothing in the reference (its beams are near-copies of one sentence): the same step for beam groups
+ *                           that are searched in turn, a group paying for every word an earlier group chose at this step
  *   grit_sample_step_f32 <- nothing in the reference (it decodes by beam search only): one word per row drawn from the tempered,
  *                           top-k / nucleus truncated word distribution, in integer arithmetic that a host form repeats exactly
  *   grit_decode_step_inputs <- CaptionGenerator.get_seq_inputs in stateful mode + the word / position embedding sum
@@ -65,7 +67,7 @@
  *   grit_jpeg_probe, grit_jpeg_entropy, grit_jpeg_reconstruct
  *                        <- PIL's Image.open(path).convert('RGB') in the dataset workers (datasets/caption/field.py:65,
  *                           tools/extract_features.py:42): libjpeg-turbo's baseline decode at its defaults
- * (none of the last fifteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ * (none of the last sixteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
  *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
@@ -77,7 +79,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 55
+#define GRIT_ABI_VERSION 56
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -822,6 +824,39 @@ int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const 
                            const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos,
                            const int* suppress, int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam,
                            int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The beam-search step of a DIVERSE (group) beam search with a Hamming penalty (Vijayakumar et al. 2016; no ancestor in the
+ * reference): the k beams are `groups` groups of g = k / groups, group i owns the source rows and the output positions
+ * [i * g, (i + 1) * g) (at the first step, cur_beam == 1, every group reads row 0), and within the step the groups are resolved
+ * in the order 0 .. groups - 1 per image.  counts[w] = how many selections of groups 0 .. i - 1 in THIS step chose word w from a
+ * LIVE source row (a finished row that survives through word 0 counts nothing; two beams choosing w count 2).  Group i scores
+ *     live row j, word w:   seq_logprob[j] + (logp[j][w] - diversity * float(counts[w]))
+ *                           one fp32 multiply, one fp32 subtract, the fp32 add of grit_beam_step_f32; never an fma
+ *     finished row j:       seq_logprob[j] at word 0, -999 elsewhere (no penalty)
+ *     banned (row, word):   -inf, penalised or not
+ * and takes its g best of its g * V candidates, value descending, equal values by ascending row * V + word.  Outputs at position
+ * i * g + r: sel_beam (the source row among all cur_beam), sel_word, new_seq_logprob = the PENALISED candidate score, new_seq_mask
+ * = the source row's liveness, picked_logprob = the unpenalised logp[sel_beam][sel_word] * liveness.  logp is one map or the
+ * mean of n_maps <= 8 maps exactly as in grit_beam_step_mean_f32 (a penalised score re-forms the mean the same way); the
+ * constraint arguments are those of grit_beam_step_con_f32, and with all of them off (ban_eos, no_repeat_ngram, no_repeat_word,
+ * n_suppress all 0) t and history are ignored.  With counts == 0 the score is grit_beam_step_f32's bit for bit, so groups == 1
+ * gives the outputs of grit_beam_step_f32 / _mean_f32 / _con_f32.  The host form is grit_amd/ops/beam.py: beam_step_groups_host.
+ *
+ * The penalty only lowers candidates, and in one source row at most |P| <= k - g of them (P: the words chosen so far in this
+ * step), so a group's g best of a row are among that row's UNPENALISED k best: stage 1 is the first launch of the plain /
+ * constrained step with k entries per list, and all the sequential group logic is the second launch, one wave per image over the
+ * same <= 128 candidates.  Workspace: grit_beam_step_workspace(B, cur_beam, k).  Limits (GRIT_ERR_UNSUPPORTED beyond them, the
+ * caller uses the host form): k <= 8, k % groups == 0, cur_beam == 1 or cur_beam == k, V >= k, diversity finite and >= 0,
+ * B <= 65535, and with any constraint on the limits of grit_beam_step_con_f32.  groups < 1: GRIT_ERR_BAD_ARG.  Two launches,
+ * no atomics on global memory, no host state, nothing uploaded; safe to capture in a HIP graph.
+ * ------------------------------------------------------------------------------------------------------ */
+int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                           const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, int groups,
+                           float diversity, const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
+                           int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
+                           int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * One step of sampled decoding after the decoder (no ancestor in the reference, whose only decoder is beam search): one word per

@@ -2,6 +2,7 @@
 (`state_dict` key, strict=False), NestedTensor batch of one, beam search, token ids -> words through vocab.json.
 
     python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth [ckpt2.pth ...]] [--vocab data/vocab.json] [--beam 5]
+                                [--groups G --diversity X] [--n-best N]
 
 Several checkpoints: one model per checkpoint, captioned together by models.caption.ensemble.Ensemble (their word
 log-probabilities averaged at every beam step).
@@ -14,7 +15,7 @@ import os
 
 import torch
 
-from grit_amd.config import beam_constraints, default_config
+from grit_amd.config import beam_constraints, beam_groups, default_config
 from grit_amd.tuning import load_tuned_gemms
 from models.caption import Transformer
 from models.caption.detector import build_detector
@@ -44,12 +45,14 @@ def build_captioner(config, device, checkpoints=('',)):
 
 
 @torch.inference_mode()
-def caption_tokens(model, image, config, beam_size=None):
-    """image [3,H,W] (already normalised) -> (tokens [1, beam_len] int64, log_probs [1, beam_len])."""
+def caption_tokens(model, image, config, beam_size=None, n_best=1):
+    """image [3,H,W] (already normalised) -> (tokens [1, beam_len] int64, log_probs [1, beam_len]); with n_best > 1 the n_best
+    best final hypotheses, [1, n_best, beam_len] each."""
     device = next(model.parameters()).device
     images = nested_tensor_from_tensor_list([image]).to(device)
     return model(images, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
-                 beam_size=beam_size or config.model.beam_size, out_size=1, return_probs=False, **beam_constraints(config))
+                 beam_size=beam_size or config.model.beam_size, out_size=n_best, return_probs=False, **beam_constraints(config),
+                 **beam_groups(config))
 
 
 @torch.inference_mode()
@@ -75,7 +78,7 @@ def caption_stream(model, batches, config, beam_size=None):
     if device.type != 'cuda':
         for samples in batches:
             yield model(samples, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
-                        beam_size=beam, out_size=1, return_probs=False, **beam_constraints(config))
+                        beam_size=beam, out_size=1, return_probs=False, **beam_constraints(config), **beam_groups(config))
         return
     # The tuned GEMM table (grit_amd/tuning.py) is switched off while two streams issue library GEMMs side by side: with it, the
     # detector stream stalls for tens of ms every few batches next to the replayed decode graph (63-91 ms per batch instead of 51,
@@ -105,7 +108,7 @@ def _caption_stream_device(model, batches, config, beam, device):
                     v.record_stream(dec_stream)
                 out = model(vis, seq=None, use_beam_search=True, max_len=config.model.beam_len,
                             eos_idx=config.model.eos_idx, beam_size=beam, out_size=1, return_probs=False,
-                            **beam_constraints(config))
+                            **beam_constraints(config), **beam_groups(config))
                 done = torch.cuda.Event()
                 done.record(dec_stream)
         finally:
@@ -164,7 +167,7 @@ def decode(tokens, vocab_path, eos_idx=3):
     return out
 
 
-def run_main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--img', required=True)
     ap.add_argument('--checkpoint', nargs='+', default=[''], help="one checkpoint, or several for an ensemble")
@@ -175,15 +178,24 @@ def run_main():
     ap.add_argument('--no-repeat-word', action='store_true', help="no word twice in a row")
     ap.add_argument('--suppress', type=int, nargs='*', default=[], metavar='ID', help="vocabulary ids that are never chosen")
     ap.add_argument('--length-penalty', type=float, default=0.0, help="rank the final beams by score / length^this (0: off)")
+    ap.add_argument('--groups', type=int, default=1, metavar='G', help="diverse beam search: G groups of beam / G beams (1: off)")
+    ap.add_argument('--diversity', type=float, default=0.0, metavar='X',
+                    help="what a group pays per earlier choice of the same word at a step")
+    ap.add_argument('--n-best', type=int, default=1, metavar='N', help="print the N best final hypotheses instead of one")
     ap.add_argument('--sample', type=int, default=0, metavar='N', help="print N sampled captions instead of the best beam")
     ap.add_argument('--temperature', type=float, default=1.0)
     ap.add_argument('--top-k', type=int, default=0, help="sample among the k most probable words only (0: all)")
     ap.add_argument('--top-p', type=float, default=1.0, help="sample inside the smallest nucleus of this mass")
     ap.add_argument('--seed', type=int, default=None, help="sampling seed (default: torch's device generator)")
-    a = ap.parse_args()
+    return ap
+
+
+def run_main():
+    a = build_parser().parse_args()
     config = default_config(**{'model.beam_min_len': a.min_len, 'model.beam_no_repeat_ngram': a.no_repeat_ngram,
                                'model.beam_no_repeat_word': a.no_repeat_word, 'model.beam_suppress': list(a.suppress),
-                               'model.beam_length_penalty': a.length_penalty})
+                               'model.beam_length_penalty': a.length_penalty, 'model.beam_groups': a.groups,
+                               'model.beam_diversity': a.diversity})
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
     model = build_captioner(config, device, a.checkpoint)
     if a.img.endswith('.npy'):
@@ -200,8 +212,12 @@ def run_main():
         for line in (decode(tokens, a.vocab, config.model.eos_idx) if os.path.exists(a.vocab) else tokens.tolist()):
             print(line)
         return
-    tokens, _ = caption_tokens(model, image, config, a.beam)
-    print(decode(tokens, a.vocab, config.model.eos_idx)[0] if os.path.exists(a.vocab) else tokens.tolist())
+    tokens, _ = caption_tokens(model, image, config, a.beam, a.n_best)
+    if a.n_best == 1:
+        print(decode(tokens, a.vocab, config.model.eos_idx)[0] if os.path.exists(a.vocab) else tokens.tolist())
+        return
+    for line in (decode(tokens[0], a.vocab, config.model.eos_idx) if os.path.exists(a.vocab) else tokens[0].tolist()):  # best first
+        print(line)
 
 
 if __name__ == "__main__":
