@@ -117,7 +117,10 @@ void msda_fwd_vec4(const float* __restrict__ value, const int64_t* __restrict__ 
         const int idc = have ? idx : LP - 1;
         const float x = __shfl(locv, 2 * idc, kWave);
         const float y = __shfl(locv, 2 * idc + 1, kWave);
-        const float wt = have ? __shfl(awv, idc, kWave) : 0.f;
+        // the shuffle stays outside the select: under `have ? ... : ...` only the lanes that have a point may run it, and a
+        // lane reads 0 from a source lane that sits out -- lane L*P - 1 whenever L*P = G*it + 1 leaves it to one group
+        const float wsrc = __shfl(awv, idc, kWave);
+        const float wt = have ? wsrc : 0.f;
         const int l = idc / P;
         const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
         const float* vl = vrow + (size_t)lsi[l] * pix_stride;
@@ -317,7 +320,10 @@ void msda_fwd_bf16_d64(const __hip_bfloat16* __restrict__ value, const int64_t* 
         const int idc = have ? idx : LP - 1;
         const float x = __shfl(locv, 2 * idc, kWave);
         const float y = __shfl(locv, 2 * idc + 1, kWave);
-        const float wt = have ? __shfl(awv, idc, kWave) : 0.f;
+        // the shuffle stays outside the select: under `have ? ... : ...` only the lanes that have a point may run it, and a
+        // lane reads 0 from a source lane that sits out -- lane L*P - 1 whenever L*P = G*it + 1 leaves it to one group
+        const float wsrc = __shfl(awv, idc, kWave);
+        const float wt = have ? wsrc : 0.f;
         const int l = idc / P;
         const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
         const __hip_bfloat16* vl = vrow + (size_t)lsi[l] * pix_stride;

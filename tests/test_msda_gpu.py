@@ -257,10 +257,12 @@ def test_d64_backward_batches_and_level_layouts(B):
     ([(9, 7), (5, 4), (3, 2)], 3, 5, 4, 1),                   # L*P = 12, 15 rows: tail wave with dead rows, M not a power of two
     ([(30, 30), (28, 28)], 8, 150, 4, 2),                     # L*P = 8: second half-row idle
     ([(16, 16), (8, 8)], 4, 9, 2, 2),                         # L*P = 4
-    ([(40, 40), (20, 20), (10, 10), (5, 5)], 8, 20, 8, 2),    # L*P = 32: wave-per-row kernel
+    ([(40, 40), (20, 20), (10, 10), (5, 5)], 8, 20, 8, 2),    # L*P = 32: beyond the op's bf16 path (L*P <= 16): map converted to f32, msda_fwd_vec4<16, 8>
 ])
 def test_bf16_forward_kernels_layouts_and_dead_corners(shapes_l, M, Lq, P, B):
-    """grit_msda_fwd_bf16 across its two kernels.  Pixel (0, 0) of every level is NaN and no live corner touches it:
+    """The op's forward on bf16 maps: msda_fwd_bf16_rows4 for L*P <= 16; at L*P = 32 the op converts the map to f32 and runs
+    msda_fwd_vec4 (the wave-per-row bf16 kernel msda_fwd_bf16_d64 is reached through the C ABI only: tests/test_msda_exact_gpu.py).
+    Pixel (0, 0) of every level is NaN and no live corner touches it:
     points are either well inside the map or entirely outside it (dead: clamped address = pixel (0, 0)), so any leak of
     a zero-weight corner into the sum shows up as NaN -- the reference never reads such corners
     (ms_deform_im2col_cuda.cuh:259-262)."""
