@@ -25,6 +25,8 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <initializer_list>
+#include <utility>
 #include "../../include/grit_hip.h"
 
 namespace {
@@ -82,33 +84,115 @@ __device__ __forceinline__ Corners<T> make_corners(T x, T y, int H, int W) {
     return c;
 }
 
+// One-row-per-wave kernels: the row (b, q, m) of the calling wave; a wave whose row is >= nrows leaves as a whole.
+// images_interleaved > 1: consecutive workgroups take the same query block of DIFFERENT images (msda_bwd_d64_pk).
+__device__ __forceinline__ int wave_row(int nblk, int images_interleaved = 1) {
+    int blk = xcd_logical_block(blockIdx.x, nblk);
+    if (images_interleaved > 1) {
+        const int per_image = nblk / images_interleaved;
+        blk = (blk % images_interleaved) * per_image + blk / images_interleaved;
+    }
+    return blk * kRowsPerBlock + (threadIdx.x >> 6);
+}
+
+// ... and what it needs to know about that row: the number of points, head m of image b.
+struct RowId {
+    int LP, m, b;
+};
+
+__device__ __forceinline__ RowId row_id(int row, int M, int L, int Lq, int P) {
+    RowId r;
+    r.LP = L * P;
+    r.m = row % M;
+    r.b = (row / M) / Lq;
+    return r;
+}
+
+// the two bf16 of a 32-bit word as floats (exact)
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+
+// v_readlane: lane `src`'s x for the whole wave (an SGPR: scalar branches, scalar addresses).  The result leaves through a
+// reference on purpose: a returned scalar is marked noundef, which lets the compiler drop the freeze it otherwise puts behind the
+// read and changes the register allocation of the D = 64 backward kernels.
+__device__ __forceinline__ void readlane(int& out, int x, int src) { out = __builtin_amdgcn_readlane(x, src); }
+__device__ __forceinline__ void readlane(float& out, float x, int src) {
+    out = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), src));
+}
+
+// What one lane holds of a (pixel, head) row in a 16-byte load: 4 floats or 8 bf16.  Raw: the slice as loaded; Acc: its
+// elements as float accumulators; Packed: the slice as stored.
+template <typename T>
+struct Slice;
+
+template <>
+struct Slice<float> {
+    static constexpr int kElems = 4;
+    typedef float4 Raw;
+    typedef float4 Acc;
+    typedef float4 Packed;
+    static __device__ __forceinline__ float& at(float4& a, int e) { return e == 0 ? a.x : e == 1 ? a.y : e == 2 ? a.z : a.w; }
+    static __device__ __forceinline__ void unpack(const float4& u, float (&f)[4]) {
+        f[0] = u.x; f[1] = u.y; f[2] = u.z; f[3] = u.w;
+    }
+    static __device__ __forceinline__ float4 pack(const float4& a) { return a; }
+};
+
+template <>
+struct Slice<__hip_bfloat16> {
+    static constexpr int kElems = 8;
+    typedef uint4 Raw;
+    struct Acc {
+        float f[8];
+    };
+    typedef __bf16 Packed __attribute__((ext_vector_type(8)));
+    static __device__ __forceinline__ float& at(Acc& a, int e) { return a.f[e]; }
+    static __device__ __forceinline__ void unpack(const uint4& u, float (&f)[8]) {
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f[2 * i] = bf16_lo(w[i]);
+            f[2 * i + 1] = bf16_hi(w[i]);
+        }
+    }
+    static __device__ __forceinline__ Packed pack(const float (&f)[8]) {
+        Packed o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (__bf16)f[e];
+        return o;
+    }
+    static __device__ __forceinline__ Packed pack(const Acc& a) { return pack(a.f); }
+};
+
 // ---------------------------------------------------------------------------------------------------
-// Forward, fast path: D = 4*LPP floats, NIT = ceil(L*P / (64/LPP)) point rounds per wave.
+// Forward, fast path, one row per wave: a (pixel, head) row of D channels is LPP lanes x 16 bytes, so the wave covers
+// G = 64 / LPP sampling points side by side; NIT = ceil(L*P / G) point rounds.  A pixel is pix_units * UNIT elements: M heads of
+// UNIT = D for the dense f32 maps (64-bit products, as those kernels always formed them), pix_el elements of UNIT = 1 for bf16.
 // ---------------------------------------------------------------------------------------------------
-template <int LPP, int NIT>
-__global__ __launch_bounds__(kWave * kRowsPerBlock)
-void msda_fwd_vec4(const float* __restrict__ value, const int64_t* __restrict__ shapes,
-                   const int64_t* __restrict__ lsi, const float* __restrict__ loc,
-                   const float* __restrict__ aw, int S, int M, int L, int Lq, int P,
-                   float* __restrict__ out, int nrows, int nblk) {
-    constexpr int D = 4 * LPP;
+template <typename T, int LPP, int NIT, int UNIT>
+__device__ __forceinline__ void msda_fwd_row(const T* value, const int64_t* shapes,
+                                             const int64_t* lsi, const float* loc,
+                                             const float* aw, int S, int M, int L, int Lq, int P,
+                                             T* out, int nrows, int nblk, int pix_units) {
+    typedef Slice<T> Sl;
+    constexpr int E = Sl::kElems;
+    constexpr int D = E * LPP;
     constexpr int G = kWave / LPP;  // sampling points handled side by side
     const int lane = threadIdx.x & (kWave - 1);
-    const int row = xcd_logical_block(blockIdx.x, nblk) * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= nrows) return;  // whole wave leaves together
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
+    const int row = wave_row(nblk);
+    if (row >= nrows) return;
+    const RowId r = row_id(row, M, L, Lq, P);
+    const int LP = r.LP;
 
     // one coalesced read of the row's 2*LP coordinates and LP weights (LP <= 32 on this path)
     const float locv = lane < 2 * LP ? loc[(size_t)row * 2 * LP + lane] : 0.f;
     const float awv = lane < LP ? aw[(size_t)row * LP + lane] : 0.f;
 
-    const int g = lane / LPP, c4 = lane % LPP;
-    const float* vrow = value + (size_t)b * S * M * D + (size_t)m * D + c4 * 4;
-    const size_t pix_stride = (size_t)M * D;
+    const int g = lane / LPP, ce = lane % LPP;
+    const T* vrow = value + (size_t)r.b * S * pix_units * UNIT + (size_t)r.m * D + ce * E;
+    const size_t pix_stride = (size_t)pix_units * UNIT;
 
-    float4 v[NIT][4];
+    typename Sl::Raw v[NIT][4];
     float cw[NIT][4];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -123,39 +207,61 @@ void msda_fwd_vec4(const float* __restrict__ value, const int64_t* __restrict__ 
         const float wt = have ? wsrc : 0.f;
         const int l = idc / P;
         const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-        const float* vl = vrow + (size_t)lsi[l] * pix_stride;
+        const T* vl = vrow + (size_t)lsi[l] * pix_stride;
         const Corners<float> c = make_corners<float>(x, y, H, W);
-        v[it][0] = *reinterpret_cast<const float4*>(vl + (size_t)c.o1 * pix_stride);
-        v[it][1] = *reinterpret_cast<const float4*>(vl + (size_t)c.o2 * pix_stride);
-        v[it][2] = *reinterpret_cast<const float4*>(vl + (size_t)c.o3 * pix_stride);
-        v[it][3] = *reinterpret_cast<const float4*>(vl + (size_t)c.o4 * pix_stride);
+        v[it][0] = *reinterpret_cast<const typename Sl::Raw*>(vl + (size_t)c.o1 * pix_stride);
+        v[it][1] = *reinterpret_cast<const typename Sl::Raw*>(vl + (size_t)c.o2 * pix_stride);
+        v[it][2] = *reinterpret_cast<const typename Sl::Raw*>(vl + (size_t)c.o3 * pix_stride);
+        v[it][3] = *reinterpret_cast<const typename Sl::Raw*>(vl + (size_t)c.o4 * pix_stride);
         cw[it][0] = c.k1 ? c.w1 * wt : 0.f;
         cw[it][1] = c.k2 ? c.w2 * wt : 0.f;
         cw[it][2] = c.k3 ? c.w3 * wt : 0.f;
         cw[it][3] = c.k4 ? c.w4 * wt : 0.f;
     }
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    typename Sl::Acc acc;
+#pragma unroll
+    for (int e = 0; e < E; ++e) Sl::at(acc, e) = 0.f;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             // select, not multiply: a non-finite value under a dropped corner must not leak
             const float w = cw[it][k];
-            const float4 t = v[it][k];
-            acc.x += w != 0.f ? w * t.x : 0.f;
-            acc.y += w != 0.f ? w * t.y : 0.f;
-            acc.z += w != 0.f ? w * t.z : 0.f;
-            acc.w += w != 0.f ? w * t.w : 0.f;
+            float f[E];
+            Sl::unpack(v[it][k], f);
+#pragma unroll
+            for (int e = 0; e < E; ++e) Sl::at(acc, e) += w != 0.f ? w * f[e] : 0.f;
         }
     }
 #pragma unroll
-    for (int off = LPP; off < kWave; off <<= 1) {
-        acc.x += __shfl_xor(acc.x, off, kWave);
-        acc.y += __shfl_xor(acc.y, off, kWave);
-        acc.z += __shfl_xor(acc.z, off, kWave);
-        acc.w += __shfl_xor(acc.w, off, kWave);
+    for (int off = LPP; off < kWave; off <<= 1)
+#pragma unroll
+        for (int e = 0; e < E; ++e) Sl::at(acc, e) += __shfl_xor(Sl::at(acc, e), off, kWave);
+    if (lane < LPP) {
+        const typename Sl::Packed o = Sl::pack(acc);
+        *reinterpret_cast<typename Sl::Packed*>(out + (size_t)row * D + lane * E) = o;
     }
-    if (lane < LPP) *reinterpret_cast<float4*>(out + (size_t)row * D + lane * 4) = acc;
+}
+
+// f32 maps, D = 4*LPP (64 or 32), dense
+template <int LPP, int NIT>
+__global__ __launch_bounds__(kWave * kRowsPerBlock)
+void msda_fwd_vec4(const float* __restrict__ value, const int64_t* __restrict__ shapes,
+                   const int64_t* __restrict__ lsi, const float* __restrict__ loc,
+                   const float* __restrict__ aw, int S, int M, int L, int Lq, int P,
+                   float* __restrict__ out, int nrows, int nblk) {
+    msda_fwd_row<float, LPP, NIT, 4 * LPP>(value, shapes, lsi, loc, aw, S, M, L, Lq, P, out, nrows, nblk, M);
+}
+
+// bf16 maps (training path: value_proj output stays bf16, no fp32 staging copy), D = 64: a (pixel, head) slice is 128 bytes =
+// 8 lanes x 16 bytes, so a wave covers 8 sampling points at once.  pix_el: elements per pixel, M*D when the map is dense.
+template <int NIT>
+__global__ __launch_bounds__(kWave * kRowsPerBlock)
+void msda_fwd_bf16_d64(const __hip_bfloat16* __restrict__ value, const int64_t* __restrict__ shapes,
+                       const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ aw,
+                       int S, int M, int L, int Lq, int P, __hip_bfloat16* __restrict__ out, int nrows, int nblk,
+                       int pix_el) {
+    msda_fwd_row<__hip_bfloat16, 8, NIT, 1>(value, shapes, lsi, loc, aw, S, M, L, Lq, P, out, nrows, nblk, pix_el);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -168,13 +274,12 @@ void msda_fwd_generic(const T* __restrict__ value, const int64_t* __restrict__ s
                       const T* __restrict__ aw, int S, int M, int D, int L, int Lq, int P,
                       T* __restrict__ out, int nrows, int nblk) {
     const int lane = threadIdx.x & (kWave - 1);
-    const int row = xcd_logical_block(blockIdx.x, nblk) * kRowsPerBlock + (threadIdx.x >> 6);
+    const int row = wave_row(nblk);
     if (row >= nrows) return;
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
+    const RowId r = row_id(row, M, L, Lq, P);
+    const int LP = r.LP;
     const size_t pix_stride = (size_t)M * D;
-    const T* vhead = value + (size_t)b * S * pix_stride + (size_t)m * D;
+    const T* vhead = value + (size_t)r.b * S * pix_stride + (size_t)r.m * D;
     const T* lrow = loc + (size_t)row * 2 * LP;
     const T* wrow = aw + (size_t)row * LP;
     for (int c = lane; c < D; c += kWave) {
@@ -213,13 +318,12 @@ void msda_bwd_generic(const T* __restrict__ value, const int64_t* __restrict__ s
                       T* __restrict__ grad_value, T* __restrict__ grad_loc, T* __restrict__ grad_aw,
                       int nrows, int nblk) {
     const int lane = threadIdx.x & (kWave - 1);
-    const int row = xcd_logical_block(blockIdx.x, nblk) * kRowsPerBlock + (threadIdx.x >> 6);
+    const int row = wave_row(nblk);
     if (row >= nrows) return;
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
+    const RowId r = row_id(row, M, L, Lq, P);
+    const int LP = r.LP;
     const size_t pix_stride = (size_t)M * D;
-    const size_t head_off = (size_t)b * S * pix_stride + (size_t)m * D;
+    const size_t head_off = (size_t)r.b * S * pix_stride + (size_t)r.m * D;
     const T* lrow = loc + (size_t)row * 2 * LP;
     const T* wrow = aw + (size_t)row * LP;
 
@@ -279,88 +383,6 @@ void msda_bwd_generic(const T* __restrict__ value, const int64_t* __restrict__ s
 }
 
 
-// ---------------------------------------------------------------------------------------------------
-// bf16 value maps (training path: value_proj output stays bf16, no fp32 staging copy).  D = 64.
-// Forward: a (pixel, head) slice is 128 bytes = 8 lanes x 16 bytes, so a wave covers 8 sampling points at once.
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(w[i] << 16);
-        f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-}
-
-template <int NIT>
-__global__ __launch_bounds__(kWave * kRowsPerBlock)
-void msda_fwd_bf16_d64(const __hip_bfloat16* __restrict__ value, const int64_t* __restrict__ shapes,
-                       const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ aw,
-                       int S, int M, int L, int Lq, int P, __hip_bfloat16* __restrict__ out, int nrows, int nblk,
-                       int pix_el) {
-    constexpr int D = 64, LPP = 8, G = 8;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int row = xcd_logical_block(blockIdx.x, nblk) * kRowsPerBlock + (threadIdx.x >> 6);
-    if (row >= nrows) return;
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
-    const float locv = lane < 2 * LP ? loc[(size_t)row * 2 * LP + lane] : 0.f;
-    const float awv = lane < LP ? aw[(size_t)row * LP + lane] : 0.f;
-    const int g = lane / LPP, c8 = lane % LPP;
-    const size_t pix_stride = (size_t)pix_el;
-    const __hip_bfloat16* vrow = value + (size_t)b * S * pix_stride + (size_t)m * D + c8 * 8;
-
-    uint4 v[NIT][4];
-    float cw[NIT][4];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int idx = it * G + g;
-        const bool have = idx < LP;
-        const int idc = have ? idx : LP - 1;
-        const float x = __shfl(locv, 2 * idc, kWave);
-        const float y = __shfl(locv, 2 * idc + 1, kWave);
-        // the shuffle stays outside the select: under `have ? ... : ...` only the lanes that have a point may run it, and a
-        // lane reads 0 from a source lane that sits out -- lane L*P - 1 whenever L*P = G*it + 1 leaves it to one group
-        const float wsrc = __shfl(awv, idc, kWave);
-        const float wt = have ? wsrc : 0.f;
-        const int l = idc / P;
-        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-        const __hip_bfloat16* vl = vrow + (size_t)lsi[l] * pix_stride;
-        const Corners<float> c = make_corners<float>(x, y, H, W);
-        v[it][0] = *reinterpret_cast<const uint4*>(vl + (size_t)c.o1 * pix_stride);
-        v[it][1] = *reinterpret_cast<const uint4*>(vl + (size_t)c.o2 * pix_stride);
-        v[it][2] = *reinterpret_cast<const uint4*>(vl + (size_t)c.o3 * pix_stride);
-        v[it][3] = *reinterpret_cast<const uint4*>(vl + (size_t)c.o4 * pix_stride);
-        cw[it][0] = c.k1 ? c.w1 * wt : 0.f;
-        cw[it][1] = c.k2 ? c.w2 * wt : 0.f;
-        cw[it][2] = c.k3 ? c.w3 * wt : 0.f;
-        cw[it][3] = c.k4 ? c.w4 * wt : 0.f;
-    }
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int it = 0; it < NIT; ++it)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float w = cw[it][k];
-            float f[8];
-            unpack8(v[it][k], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += w != 0.f ? w * f[e] : 0.f;
-        }
-#pragma unroll
-    for (int off = LPP; off < kWave; off <<= 1)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += __shfl_xor(acc[e], off, kWave);
-    if (lane < LPP) {
-        typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-        v8bf o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)acc[e];
-        *reinterpret_cast<v8bf*>(out + (size_t)row * D + lane * 8) = o;
-    }
-}
-
 // Forward for bf16 maps, D = 64, L*P <= 16 -- the training-step shape -- with the gather latency taken off the
 // critical path.  The wave-per-row kernel above is latency x occupancy bound (two dependent HBM hops per wave:
 // sampling geometry, then the corners; ~5 us of wave lifetime for < 1 us of work).  Here a wave owns FOUR rows:
@@ -372,6 +394,48 @@ void msda_fwd_bf16_d64(const __hip_bfloat16* __restrict__ value, const int64_t* 
 //     time, addresses = uniform base + 32-bit offsets;
 //   * fold: the two halves meet in ONE DPP row_ror:8 add per channel (no LDS shuffles), lanes 0-7 of each row store
 //     the 128-byte output row.
+//
+// Rows4Point is the geometry stage, shared with msda_bwd_rows4: the point a lane computes for its wave's four rows.
+struct Rows4Point {
+    int row, p;               // row r0 + (lane >> 4), point lane & 15
+    bool valid;               // the row exists and has a point p
+    int rc;                   // row, clamped into the map (what the loads use)
+    float wt;                 // attention weight, 0 when !valid
+    int H, W;
+    uint32_t base, pix;       // byte offset of the level's (image, head) map from `value`, bytes per pixel
+    Corners<float> c;
+};
+
+__device__ __forceinline__ Rows4Point rows4_point(int r0, int lane, int nrows, const int64_t* shapes,
+                                                  const int64_t* lsi, const float* loc,
+                                                  const float* aw, int S, int M, int L, int Lq, int P,
+                                                  int pix_el) {
+    constexpr int D = 64;
+    const int LP = L * P;
+    Rows4Point g;
+    g.row = r0 + (lane >> 4); g.p = lane & 15;
+    g.valid = g.row < nrows && g.p < LP;
+    g.rc = min(g.row, nrows - 1);
+    const int pc = min(g.p, LP - 1);
+    const float2 xy = *reinterpret_cast<const float2*>(loc + ((size_t)g.rc * LP + pc) * 2);
+    g.wt = g.valid ? aw[(size_t)g.rc * LP + pc] : 0.f;
+    const int l = pc / P;
+    g.H = (int)shapes[2 * l]; g.W = (int)shapes[2 * l + 1];
+    const uint32_t m = g.rc % M, b = (g.rc / M) / Lq;
+    // byte offsets from `value` (pix_el elements per pixel, M*D when the map is dense); the launcher checks that
+    // the whole map fits 32 bits
+    g.pix = (uint32_t)pix_el * 2;
+    g.base = (b * (uint32_t)S + (uint32_t)lsi[l]) * g.pix + m * (D * 2);
+    g.c = make_corners<float>(xy.x, xy.y, g.H, g.W);
+    return g;
+}
+
+// byte offset from `value` of the (pixel, head) slice at clamped pixel `o` of the point's level: always a legal address
+__device__ __forceinline__ uint32_t rows4_offset(const Rows4Point& g, int o) { return g.base + o * g.pix; }
+
+// where the 8 points that this lane's half (8 lanes) of its 16-lane row walks are parked in the wave's tile
+__device__ __forceinline__ int rows4_half_points(int lane) { return (lane & 48) + (lane & 8); }
+
 template <int BATCH>
 __global__ __launch_bounds__(256)
 void msda_fwd_bf16_rows4(const __hip_bfloat16* __restrict__ value, const int64_t* __restrict__ shapes,
@@ -384,36 +448,18 @@ void msda_fwd_bf16_rows4(const __hip_bfloat16* __restrict__ value, const int64_t
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r0 = (xcd_logical_block(blockIdx.x, nblk) * 4 + wave) * 4;
     if (r0 >= nrows) return;
-    const int LP = L * P;
     {
-        const int row = r0 + (lane >> 4), p = lane & 15;
-        const bool valid = row < nrows && p < LP;
-        const int rc = min(row, nrows - 1), pc = min(p, LP - 1);
-#ifdef GRIT_MSDA_NT
-        typedef float v2f_t __attribute__((ext_vector_type(2)));
-        const v2f_t xyv = __builtin_nontemporal_load(reinterpret_cast<const v2f_t*>(loc + ((size_t)rc * LP + pc) * 2));
-        const float2 xy = make_float2(xyv[0], xyv[1]);
-        const float wt = valid ? __builtin_nontemporal_load(aw + (size_t)rc * LP + pc) : 0.f;
-#else
-        const float2 xy = *reinterpret_cast<const float2*>(loc + ((size_t)rc * LP + pc) * 2);
-        const float wt = valid ? aw[(size_t)rc * LP + pc] : 0.f;
-#endif
-        const int l = pc / P;
-        const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-        const uint32_t m = rc % M, b = (rc / M) / Lq;
-        // byte offsets from `value` (pix_el elements per pixel, M*D when the map is dense); the launcher checks that
-        // the whole map fits 32 bits
-        const uint32_t pix = (uint32_t)pix_el * 2;
-        const uint32_t base = (b * (uint32_t)S + (uint32_t)lsi[l]) * pix + m * (D * 2);
-        const Corners<float> c = make_corners<float>(xy.x, xy.y, H, W);
-        geo[wave][lane][0] = make_uint4(base + c.o1 * pix, base + c.o2 * pix, base + c.o3 * pix, base + c.o4 * pix);
+        const Rows4Point pt = rows4_point(r0, lane, nrows, shapes, lsi, loc, aw, S, M, L, Lq, P, pix_el);
+        const Corners<float>& c = pt.c;
+        const float wt = pt.wt;
+        geo[wave][lane][0] = make_uint4(rows4_offset(pt, c.o1), rows4_offset(pt, c.o2), rows4_offset(pt, c.o3), rows4_offset(pt, c.o4));
         geo[wave][lane][1] = make_uint4(__float_as_uint(c.k1 ? c.w1 * wt : 0.f), __float_as_uint(c.k2 ? c.w2 * wt : 0.f),
                                         __float_as_uint(c.k3 ? c.w3 * wt : 0.f), __float_as_uint(c.k4 ? c.w4 * wt : 0.f));
     }
     __builtin_amdgcn_wave_barrier();
     const int c8 = lane & 7;
     const uint32_t cb = c8 * 16;
-    const uint4(*g)[2] = &geo[wave][(lane & 48) + (lane & 8)];  // this half's 8 points of this row
+    const uint4(*g)[2] = &geo[wave][rows4_half_points(lane)];  // this half's 8 points of this row
     const char* vb = reinterpret_cast<const char*>(value);
     typedef float f2 __attribute__((ext_vector_type(2)));
     f2 acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};  // channels (2j, 2j+1): v_pk_fma_f32
@@ -443,7 +489,7 @@ void msda_fwd_bf16_rows4(const __hip_bfloat16* __restrict__ value, const int64_t
                 const f2 w2 = {w[i][k], w[i][k]};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f2 f = {__uint_as_float(d[j] << 16), __uint_as_float(d[j] & 0xffff0000u)};
+                    const f2 f = {bf16_lo(d[j]), bf16_hi(d[j])};
                     acc[j] = __builtin_elementwise_fma(w2, f, acc[j]);
                 }
             }
@@ -456,15 +502,8 @@ void msda_fwd_bf16_rows4(const __hip_bfloat16* __restrict__ value, const int64_t
     }
     const int row = r0 + (lane >> 4);
     if ((lane & 8) == 0 && row < nrows) {
-        typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-        v8bf o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (__bf16)r[e];
-#ifdef GRIT_MSDA_NT
-        __builtin_nontemporal_store(o, reinterpret_cast<v8bf*>(out + (size_t)row * D + c8 * 8));
-#else
-        *reinterpret_cast<v8bf*>(out + (size_t)row * D + c8 * 8) = o;
-#endif
+        const Slice<__hip_bfloat16>::Packed o = Slice<__hip_bfloat16>::pack(r);
+        *reinterpret_cast<Slice<__hip_bfloat16>::Packed*>(out + (size_t)row * D + c8 * 8) = o;
     }
 }
 
@@ -488,26 +527,18 @@ void msda_bwd_rows4(const __hip_bfloat16* __restrict__ value, const int64_t* __r
     const int r0 = (xcd_logical_block(blockIdx.x, nblk) * 4 + wave) * 4;
     if (r0 >= nrows) return;
     const int LP = L * P;
-    const int row = r0 + (lane >> 4), p = lane & 15;
-    const bool valid = row < nrows && p < LP;
-    const int rc = min(row, nrows - 1), pc = min(p, LP - 1);
-    const float2 xy = *reinterpret_cast<const float2*>(loc + ((size_t)rc * LP + pc) * 2);
-    const float wt = valid ? aw[(size_t)rc * LP + pc] : 0.f;
-    const int l = pc / P;
-    const int H = (int)shapes[2 * l], W = (int)shapes[2 * l + 1];
-    const Corners<float> c = make_corners<float>(xy.x, xy.y, H, W);
-    {
-        const uint32_t m = rc % M, b = (rc / M) / Lq;
-        const uint32_t pix = (uint32_t)pix_el * 2;
-        const uint32_t base = (b * (uint32_t)S + (uint32_t)lsi[l]) * pix + m * (D * 2);
-        // a dead corner keeps its clamped (legal) address; bit 0 of the byte offset marks it (offsets are multiples of 16)
-        geo[wave][lane] = make_uint4((base + c.o1 * pix) | (c.k1 ? 0u : 1u), (base + c.o2 * pix) | (c.k2 ? 0u : 1u),
-                                     (base + c.o3 * pix) | (c.k3 ? 0u : 1u), (base + c.o4 * pix) | (c.k4 ? 0u : 1u));
-    }
+    const Rows4Point pt = rows4_point(r0, lane, nrows, shapes, lsi, loc, aw, S, M, L, Lq, P, pix_el);
+    const Corners<float>& c = pt.c;
+    const int row = pt.row, p = pt.p, rc = pt.rc, H = pt.H, W = pt.W;
+    const bool valid = pt.valid;
+    const float wt = pt.wt;
+    // a dead corner keeps its clamped (legal) address; bit 0 of the byte offset marks it (offsets are multiples of 16)
+    geo[wave][lane] = make_uint4(rows4_offset(pt, c.o1) | (c.k1 ? 0u : 1u), rows4_offset(pt, c.o2) | (c.k2 ? 0u : 1u),
+                                 rows4_offset(pt, c.o3) | (c.k3 ? 0u : 1u), rows4_offset(pt, c.o4) | (c.k4 ? 0u : 1u));
     __builtin_amdgcn_wave_barrier();
     const int c8 = lane & 7;
     const uint32_t cb = c8 * 16;
-    const uint4* g = &geo[wave][(lane & 48) + (lane & 8)];  // this half's 8 points of this row
+    const uint4* g = &geo[wave][rows4_half_points(lane)];  // this half's 8 points of this row
     const char* vb = reinterpret_cast<const char*>(value);
     typedef float f2 __attribute__((ext_vector_type(2)));
     f2 go2[4];
@@ -515,7 +546,7 @@ void msda_bwd_rows4(const __hip_bfloat16* __restrict__ value, const int64_t* __r
         const uint4 gq = *reinterpret_cast<const uint4*>(grad_out + (size_t)rc * D + c8 * 8);
         const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) go2[j] = f2{__uint_as_float(gw[j] << 16), __uint_as_float(gw[j] & 0xffff0000u)};
+        for (int j = 0; j < 4; ++j) go2[j] = f2{bf16_lo(gw[j]), bf16_hi(gw[j])};
     }
     float d[32];  // d[4 i + k]: this lane's 8 channels of <grad_out, corner k of this half's point i>
 #pragma unroll
@@ -542,7 +573,7 @@ void msda_bwd_rows4(const __hip_bfloat16* __restrict__ value, const int64_t* __r
                 f2 a = {0.f, 0.f};
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    a = __builtin_elementwise_fma(go2[j], f2{__uint_as_float(w4[j] << 16), __uint_as_float(w4[j] & 0xffff0000u)}, a);
+                    a = __builtin_elementwise_fma(go2[j], f2{bf16_lo(w4[j]), bf16_hi(w4[j])}, a);
                 d[4 * (it0 + i) + k] = a.x + a.y;
             }
         }
@@ -594,6 +625,69 @@ __device__ __forceinline__ void halve_step(float (&v)[64], int lane, int off) {
     }
 }
 
+// The tail of the one-row-per-wave backward kernels: every lane holds its channels' share of part[0,16) = grad_attn_w per
+// point and part[16,48) = grad_loc (x, y) per point; the butterfly sums them over the wave and each lane stores the one it owns.
+__device__ __forceinline__ void store_row_grads(float (&part)[64], int lane, int row, int LP, float* grad_loc,
+                                                float* grad_aw) {
+    halve_step<64>(part, lane, 32);
+    halve_step<32>(part, lane, 16);
+    halve_step<16>(part, lane, 8);
+    halve_step<8>(part, lane, 4);
+    halve_step<4>(part, lane, 2);
+    halve_step<2>(part, lane, 1);
+    const int j = (int)(__brev((unsigned)lane) >> 26);  // index of the value this lane now owns
+    if (j < LP) grad_aw[(size_t)row * LP + j] = part[0];
+    else if (j >= 16 && j < 16 + 2 * LP) grad_loc[(size_t)row * 2 * LP + (j - 16)] = part[0];
+}
+
+// Geometry ONCE per row, point p on lane p (the reference and the generic kernel redo it on every channel lane); the per-point
+// scalars then reach all lanes through readlane.  Lanes past the row's last point hold a copy of it with flags = 0, wt = 0.
+struct LanePoint {
+    int e1, e2, e3, e4;  // cells of the four corners inside one (image, head) map: level start + clamped corner offset
+    int flags;           // bit k - 1: corner k lies inside the map
+    float lh, lw, wt;    // bilinear fractions, attention weight
+    float fW, fH;        // W * wt, H * wt
+};
+
+__device__ __forceinline__ LanePoint lane_point(const int64_t* shapes, const int64_t* lsi,
+                                                const float* loc, const float* aw, int row, int lane,
+                                                int LP, int P) {
+    const int pi = min(lane, LP - 1), pl = pi / P;
+    const int pH = (int)shapes[2 * pl], pW = (int)shapes[2 * pl + 1], pst = (int)lsi[pl];
+    const float px = loc[(size_t)row * 2 * LP + 2 * pi], py = loc[(size_t)row * 2 * LP + 2 * pi + 1];
+    const float pwt = lane < LP ? aw[(size_t)row * LP + pi] : 0.f;
+    const Corners<float> c = make_corners<float>(px, py, pH, pW);
+    LanePoint pt;
+    pt.e1 = pst + c.o1; pt.e2 = pst + c.o2; pt.e3 = pst + c.o3; pt.e4 = pst + c.o4;
+    pt.flags = lane < LP ? ((c.k1 ? 1 : 0) | (c.k2 ? 2 : 0) | (c.k3 ? 4 : 0) | (c.k4 ? 8 : 0)) : 0;
+    pt.lh = c.lh; pt.lw = c.lw; pt.wt = pwt;
+    pt.fW = (float)pW * pwt; pt.fH = (float)pH * pwt;
+    return pt;
+}
+
+// point p of the row (the one lane p computed), the same on every lane
+__device__ __forceinline__ LanePoint point_at(const LanePoint& pt, int p) {
+    LanePoint u;
+    readlane(u.flags, pt.flags, p);
+    readlane(u.e1, pt.e1, p); readlane(u.e2, pt.e2, p); readlane(u.e3, pt.e3, p); readlane(u.e4, pt.e4, p);
+    readlane(u.lh, pt.lh, p); readlane(u.lw, pt.lw, p); readlane(u.wt, pt.wt, p);
+    readlane(u.fW, pt.fW, p); readlane(u.fH, pt.fH, p);
+    return u;
+}
+
+// points p and q of the row have the same live corners in the same cells; read and compared field by field, as far as they agree
+__device__ __forceinline__ bool same_at(int x, int p, int q) {
+    int a, b;
+    readlane(a, x, p);
+    readlane(b, x, q);
+    return a == b;
+}
+
+__device__ __forceinline__ bool same_cells(const LanePoint& pt, int p, int q) {
+    return same_at(pt.e1, p, q) && same_at(pt.e2, p, q) && same_at(pt.e3, p, q) && same_at(pt.e4, p, q) &&
+           same_at(pt.flags, p, q);
+}
+
 // Backward for D = 64, L*P <= 16, value / grad_out in f32 or bf16: one wave per (b, q, m) row, lane = channel.
 // (Measured alternatives, see profiles/r01/msda_bwd_ablation.txt: keeping the coarse levels' gradient in LDS with
 //  ds_add_f32 is SLOWER than global float atomics on gfx950 -- ~150 cycles per LDS float-atomic wave instruction --
@@ -606,27 +700,16 @@ void msda_bwd_d64(const VT* __restrict__ value, const int64_t* __restrict__ shap
                   float* __restrict__ grad_aw, int nrows, int nblk) {
     constexpr int D = 64, kMaxLP = 16;
     const int lane = threadIdx.x & (kWave - 1);
-    const int row = xcd_logical_block(blockIdx.x, nblk) * kRowsPerBlock + (threadIdx.x >> 6);
+    const int row = wave_row(nblk);
     if (row >= nrows) return;
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
+    const RowId r = row_id(row, M, L, Lq, P);
+    const int LP = r.LP;
     const int pix_stride = M * D;
-    const size_t head_off = (size_t)b * S * pix_stride + (size_t)m * D;
+    const size_t head_off = (size_t)r.b * S * pix_stride + (size_t)r.m * D;
     const VT* vhead = value + head_off + lane;
     float* ghead = grad_value + head_off + lane;
-
-    // geometry ONCE per row, point p on lane p (the reference and the generic kernel redo it on every channel lane);
-    // the per-point scalars then reach all lanes through v_readlane (SGPRs: scalar branches, scalar addresses)
-    const int pi = min(lane, LP - 1), pl = pi / P;
-    const int pH = (int)shapes[2 * pl], pW = (int)shapes[2 * pl + 1], pst = (int)lsi[pl];
     const float go = ldv(grad_out + (size_t)row * D + lane);
-    const float px = loc[(size_t)row * 2 * LP + 2 * pi], py = loc[(size_t)row * 2 * LP + 2 * pi + 1];
-    const float pwt = lane < LP ? aw[(size_t)row * LP + pi] : 0.f;
-    const Corners<float> c = make_corners<float>(px, py, pH, pW);
-    const int e1 = pst + c.o1, e2 = pst + c.o2, e3 = pst + c.o3, e4 = pst + c.o4;
-    const int flags = lane < LP ? ((c.k1 ? 1 : 0) | (c.k2 ? 2 : 0) | (c.k3 ? 4 : 0) | (c.k4 ? 8 : 0)) : 0;
-    const float fW = (float)pW * pwt, fH = (float)pH * pwt;
+    const LanePoint pt = lane_point(shapes, lsi, loc, aw, row, lane, LP, P);
 
     float part[64];  // [0,16): grad_attn_w per point, [16,48): grad_loc (x, y) per point, rest zero
 #pragma unroll
@@ -634,14 +717,9 @@ void msda_bwd_d64(const VT* __restrict__ value, const int64_t* __restrict__ shap
 #pragma unroll
     for (int p = 0; p < kMaxLP; ++p) {
         if (p < LP) {
-            const int f = __builtin_amdgcn_readlane(flags, p);
-            const int s1 = __builtin_amdgcn_readlane(e1, p), s2 = __builtin_amdgcn_readlane(e2, p);
-            const int s3 = __builtin_amdgcn_readlane(e3, p), s4 = __builtin_amdgcn_readlane(e4, p);
-            const float lh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lh), p));
-            const float lw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lw), p));
-            const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pwt), p));
-            const float sW = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fW), p));
-            const float sH = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fH), p));
+            const LanePoint u = point_at(pt, p);
+            const int f = u.flags, s1 = u.e1, s2 = u.e2, s3 = u.e3, s4 = u.e4;
+            const float lh = u.lh, lw = u.lw, wt = u.wt, sW = u.fW, sH = u.fH;
             const float hh = 1.f - lh, hw = 1.f - lw;
             // clamped indices are always legal: load all four, select by the validity bits
             const float r1 = ldv(vhead + (size_t)s1 * pix_stride), r2 = ldv(vhead + (size_t)s2 * pix_stride);
@@ -660,15 +738,7 @@ void msda_bwd_d64(const VT* __restrict__ value, const int64_t* __restrict__ shap
             part[17 + 2 * p] = sH * gh * go;
         }
     }
-    halve_step<64>(part, lane, 32);
-    halve_step<32>(part, lane, 16);
-    halve_step<16>(part, lane, 8);
-    halve_step<8>(part, lane, 4);
-    halve_step<4>(part, lane, 2);
-    halve_step<2>(part, lane, 1);
-    const int j = (int)(__brev((unsigned)lane) >> 26);  // index of the value this lane now owns
-    if (j < LP) grad_aw[(size_t)row * LP + j] = part[0];
-    else if (j >= 16 && j < 16 + 2 * LP) grad_loc[(size_t)row * 2 * LP + (j - 16)] = part[0];
+    store_row_grads(part, lane, row, LP, grad_loc, grad_aw);
 }
 
 // Backward for bf16 maps with the value gradient accumulated IN bf16 by packed atomics (global_atomic_pk_add_bf16: two
@@ -687,10 +757,75 @@ void msda_bwd_d64(const VT* __restrict__ value, const int64_t* __restrict__ shap
 // lane that computed the point.  Every cell a row touches is marked in cell_flags[B, S, M] (plain byte stores of 1: all
 // writers write the same value), so msda_stage_flush visits the touched cells only: it rounds them once into the bf16
 // gradient map and leaves stage and flags zeroed for the next launch.
-// MODE 0: packed-bf16 atomics into grad_value; MODE 1 (STAGE): f32 atomics into the staging map; MODE 2: NO scatter at all --
-// the row walk only produces grad_loc / grad_attn_w, the value gradient comes from the gather-form kernels further down
-// (msda_bwd_index / msda_bwd_gather).
-template <int MODE>
+enum class Scatter {
+    kPacked,  // packed-bf16 atomics into grad_value
+    kStaged,  // (STAGE) f32 atomics into the staging map
+    kNone,    // NO scatter at all: the row walk only produces grad_loc / grad_attn_w, the value gradient comes from the
+              // gather-form kernel further down (msda_bwd_value)
+};
+
+// The four bilinear weights x attention weight of a point.
+struct CornerWeights {
+    float w1, w2, w3, w4;
+};
+
+__device__ __forceinline__ CornerWeights corner_weights(const LanePoint& u) {
+    const float hh = (1.f - u.lh) * u.wt, lhw = u.lh * u.wt;
+    return CornerWeights{hh * (1.f - u.lw), hh * u.lw, lhw * (1.f - u.lw), lhw * u.lw};
+}
+
+__device__ __forceinline__ void add(CornerWeights& a, const CornerWeights& b) {
+    a.w1 += b.w1; a.w2 += b.w2; a.w3 += b.w3; a.w4 += b.w4;
+}
+
+// w += corner_weights(u), as the merged sums have always been written: each product and its add in one expression.  With this
+// compiler add(w, corner_weights(u)) gives the same fma's and the same sums; the second spelling exists for register allocation
+// alone (the packed kernel takes 94 instead of 92 VGPRs without it, at equal occupancy, profiles/msda_refactor/README.md).
+__device__ __forceinline__ void add_corner_weights(CornerWeights& w, const LanePoint& u) {
+    const float hh = (1.f - u.lh) * u.wt, lhw = u.lh * u.wt;
+    w.w1 += hh * (1.f - u.lw); w.w2 += hh * u.lw; w.w3 += lhw * (1.f - u.lw); w.w4 += lhw * u.lw;
+}
+
+// the live corners of point u take w x (this lane's channel of grad_out) in f32: shead is the lane's channel of the staging map
+__device__ __forceinline__ void staged_atomics(float* shead, int pix_stride, const LanePoint& u, const CornerWeights& w,
+                                               float go_ch) {
+    if (u.flags & 1) atomic_add_fast(shead + (size_t)u.e1 * pix_stride, w.w1 * go_ch);
+    if (u.flags & 2) atomic_add_fast(shead + (size_t)u.e2 * pix_stride, w.w2 * go_ch);
+    if (u.flags & 4) atomic_add_fast(shead + (size_t)u.e3 * pix_stride, w.w3 * go_ch);
+    if (u.flags & 8) atomic_add_fast(shead + (size_t)u.e4 * pix_stride, w.w4 * go_ch);
+}
+
+// the live corners of point u take w x (this lane's channel pair go0, go1) as one packed bf16 atomic each
+__device__ __forceinline__ void packed_atomics(__hip_bfloat16* ghead, int pix_stride, const LanePoint& u, const CornerWeights& w,
+                                               float go0, float go1) {
+    typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+    typedef v2bf __attribute__((address_space(1))) * gv2bf_ptr;
+    if (u.flags & 1) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)u.e1 * pix_stride), v2bf{(__bf16)(w.w1 * go0), (__bf16)(w.w1 * go1)});
+    if (u.flags & 2) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)u.e2 * pix_stride), v2bf{(__bf16)(w.w2 * go0), (__bf16)(w.w2 * go1)});
+    if (u.flags & 4) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)u.e3 * pix_stride), v2bf{(__bf16)(w.w3 * go0), (__bf16)(w.w3 * go1)});
+    if (u.flags & 8) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)u.e4 * pix_stride), v2bf{(__bf16)(w.w4 * go0), (__bf16)(w.w4 * go1)});
+}
+
+// x of point 2i on the lower half of the wave, of point 2i + 1 on the upper
+template <typename T>
+__device__ __forceinline__ void pick(T& out, T x, int i, bool odd) {
+    if (odd) readlane(out, x, 2 * i + 1);
+    else readlane(out, x, 2 * i);
+}
+
+// Step i of a walk that gives the even points to the lower half of the wave and the odd ones to the upper: this half's point,
+// with flags = 0 where the upper half has none (the last step of an odd L*P).
+__device__ __forceinline__ LanePoint point_of_half(const LanePoint& pt, int i, bool odd, int LP) {
+    LanePoint u;
+    if (2 * i + 1 < LP || !odd) pick(u.flags, pt.flags, i, odd);
+    else u.flags = 0;
+    pick(u.e1, pt.e1, i, odd); pick(u.e2, pt.e2, i, odd); pick(u.e3, pt.e3, i, odd); pick(u.e4, pt.e4, i, odd);
+    pick(u.lh, pt.lh, i, odd); pick(u.lw, pt.lw, i, odd); pick(u.wt, pt.wt, i, odd);
+    pick(u.fW, pt.fW, i, odd); pick(u.fH, pt.fH, i, odd);
+    return u;
+}
+
+template <Scatter MODE>
 __global__ __launch_bounds__(kWave * kRowsPerBlock)
 void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __restrict__ shapes,
                      const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ aw,
@@ -699,23 +834,15 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
                      int nrows, int nblk, int images_interleaved, int merge_disabled, int pix_el,
                      float* __restrict__ stage, unsigned char* __restrict__ cell_flags) {
     constexpr int D = 64, kMaxLP = 16;
-    constexpr bool STAGE = MODE == 1, PACKED = MODE == 0;
-    typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-    typedef v2bf __attribute__((address_space(1))) * gv2bf_ptr;
+    constexpr bool STAGE = MODE == Scatter::kStaged, PACKED = MODE == Scatter::kPacked;
+    // image-interleaved order (wave_row): workgroups in flight together then scatter into different value maps.  A freshly
+    // initialised GRIT puts every query's reference point near the image centre, so neighbouring queries of one image pile
+    // their atomics onto the same few hundred pixels.
     const int lane = threadIdx.x & (kWave - 1);
-    int blk = xcd_logical_block(blockIdx.x, nblk);
-    if (images_interleaved > 1) {
-        // consecutive workgroups take the same query block of DIFFERENT images: workgroups in flight together then
-        // scatter into different value maps.  A freshly initialised GRIT puts every query's reference point near the
-        // image centre, so neighbouring queries of one image pile their atomics onto the same few hundred pixels.
-        const int per_image = nblk / images_interleaved;
-        blk = (blk % images_interleaved) * per_image + blk / images_interleaved;
-    }
-    const int row = blk * kRowsPerBlock + (threadIdx.x >> 6);
+    const int row = wave_row(nblk, images_interleaved);
     if (row >= nrows) return;
-    const int LP = L * P;
-    const int m = row % M;
-    const int b = (row / M) / Lq;
+    const RowId r = row_id(row, M, L, Lq, P);
+    const int LP = r.LP, m = r.m, b = r.b;
     const int pix_stride = pix_el;  // elements per pixel: M * D for a dense map
     const bool odd = lane >= 32;            // this half's points: 2i + odd
     const int cp = lane & 31;               // channels 2cp, 2cp + 1
@@ -723,17 +850,9 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
     const __hip_bfloat16* vhead = value + head_off;
     __hip_bfloat16* ghead = grad_value + head_off;
 
-    // geometry once per row, point p on lane p
-    const int pi = min(lane, LP - 1), pl = pi / P;
-    const int pH = (int)shapes[2 * pl], pW = (int)shapes[2 * pl + 1], pst = (int)lsi[pl];
     const uint32_t gob = *reinterpret_cast<const uint32_t*>(grad_out + (size_t)row * D + 2 * cp);
-    const float go0 = __uint_as_float(gob << 16), go1 = __uint_as_float(gob & 0xffff0000u);
-    const float px = loc[(size_t)row * 2 * LP + 2 * pi], py = loc[(size_t)row * 2 * LP + 2 * pi + 1];
-    const float pwt = lane < LP ? aw[(size_t)row * LP + pi] : 0.f;
-    const Corners<float> c = make_corners<float>(px, py, pH, pW);
-    const int e1 = pst + c.o1, e2 = pst + c.o2, e3 = pst + c.o3, e4 = pst + c.o4;
-    const int flags = lane < LP ? ((c.k1 ? 1 : 0) | (c.k2 ? 2 : 0) | (c.k3 ? 4 : 0) | (c.k4 ? 8 : 0)) : 0;
-    const float fW = (float)pW * pwt, fH = (float)pH * pwt;
+    const float go0 = bf16_lo(gob), go1 = bf16_hi(gob);
+    const LanePoint pt = lane_point(shapes, lsi, loc, aw, row, lane, LP, P);
     // STAGE: channel = lane view of this row's output gradient and of the staging map; touched cells flagged by the lane
     // that owns the point
     float go_ch = 0.f;
@@ -743,33 +862,24 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
         shead = stage + (size_t)b * S * M * D + (size_t)m * D + lane;
         if (lane < LP) {
             unsigned char* fl = cell_flags + (size_t)b * S * M + m;
-            if (flags & 1) fl[(size_t)e1 * M] = 1;
-            if (flags & 2) fl[(size_t)e2 * M] = 1;
-            if (flags & 4) fl[(size_t)e3 * M] = 1;
-            if (flags & 8) fl[(size_t)e4 * M] = 1;
+            if (pt.flags & 1) fl[(size_t)pt.e1 * M] = 1;
+            if (pt.flags & 2) fl[(size_t)pt.e2 * M] = 1;
+            if (pt.flags & 4) fl[(size_t)pt.e3 * M] = 1;
+            if (pt.flags & 8) fl[(size_t)pt.e4 * M] = 1;
         }
     }
-#define GRIT_RLF(x, p) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), (p)))
-#define GRIT_STAGE_ADD(f_, s1_, s2_, s3_, s4_, W1_, W2_, W3_, W4_)                                   \
-    do {                                                                                             \
-        if ((f_) & 1) atomic_add_fast(shead + (size_t)(s1_) * (M * D), (W1_) * go_ch);               \
-        if ((f_) & 2) atomic_add_fast(shead + (size_t)(s2_) * (M * D), (W2_) * go_ch);               \
-        if ((f_) & 4) atomic_add_fast(shead + (size_t)(s3_) * (M * D), (W3_) * go_ch);               \
-        if ((f_) & 8) atomic_add_fast(shead + (size_t)(s4_) * (M * D), (W4_) * go_ch);               \
-    } while (0)
 
     float part[64];  // [0,16): grad_attn_w per point, [16,48): grad_loc (x, y) per point, rest zero
 #pragma unroll
     for (int i = 0; i < 64; ++i) part[i] = 0.f;
-#define GRIT_PICK_I(x, i) (odd ? __builtin_amdgcn_readlane((x), 2 * (i) + 1) : __builtin_amdgcn_readlane((x), 2 * (i)))
-#define GRIT_PICK_F(x, i) __int_as_float(GRIT_PICK_I(__float_as_int(x), i))
     // all gathers of the row first (in the training step the value map is cold: one HBM round trip per row instead of
     // one per point pair), then the arithmetic and the scatters
     uint32_t rr[kMaxLP / 2][4];
 #pragma unroll
     for (int i = 0; i < kMaxLP / 2; ++i) {
         if (2 * i < LP) {
-            const int s1 = GRIT_PICK_I(e1, i), s2 = GRIT_PICK_I(e2, i), s3 = GRIT_PICK_I(e3, i), s4 = GRIT_PICK_I(e4, i);
+            const LanePoint u = point_of_half(pt, i, odd, LP);
+            const int s1 = u.e1, s2 = u.e2, s3 = u.e3, s4 = u.e4;
             rr[i][0] = *reinterpret_cast<const uint32_t*>(vhead + (size_t)s1 * pix_stride);
             rr[i][1] = *reinterpret_cast<const uint32_t*>(vhead + (size_t)s2 * pix_stride);
             rr[i][2] = *reinterpret_cast<const uint32_t*>(vhead + (size_t)s3 * pix_stride);
@@ -781,7 +891,7 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
     // per level with wave-uniform compares and the bilinear weights are summed first -- 4 half-wave atomics per level
     // instead of 8 full-wave ones, and a quarter of the same-address traffic.  Levels whose points differ take the
     // per-point path unchanged.
-    const bool mergeable = MODE != 2 && P == 4 && LP == kMaxLP && !merge_disabled;
+    const bool mergeable = MODE != Scatter::kNone && P == 4 && LP == kMaxLP && !merge_disabled;
     bool merged = false;
 #pragma unroll
     for (int i = 0; i < kMaxLP / 2; ++i) {
@@ -790,101 +900,56 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
                 merged = mergeable;
                 const int p0 = 2 * i;
 #pragma unroll
-                for (int k = 1; k < 4; ++k)
-                    merged = merged && __builtin_amdgcn_readlane(e1, p0) == __builtin_amdgcn_readlane(e1, p0 + k) &&
-                             __builtin_amdgcn_readlane(e2, p0) == __builtin_amdgcn_readlane(e2, p0 + k) &&
-                             __builtin_amdgcn_readlane(e3, p0) == __builtin_amdgcn_readlane(e3, p0 + k) &&
-                             __builtin_amdgcn_readlane(e4, p0) == __builtin_amdgcn_readlane(e4, p0 + k) &&
-                             __builtin_amdgcn_readlane(flags, p0) == __builtin_amdgcn_readlane(flags, p0 + k);
+                for (int k = 1; k < 4; ++k) merged = merged && same_cells(pt, p0, p0 + k);
                 if (merged) {
-                    float W1 = 0.f, W2 = 0.f, W3 = 0.f, W4 = 0.f;
+                    CornerWeights sum = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float lh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lh), p0 + k));
-                        const float lw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lw), p0 + k));
-                        const float wt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pwt), p0 + k));
-                        const float hh = (1.f - lh) * wt, lhw = lh * wt;
-                        W1 += hh * (1.f - lw); W2 += hh * lw; W3 += lhw * (1.f - lw); W4 += lhw * lw;
-                    }
-                    const int f = __builtin_amdgcn_readlane(flags, p0);
+                    for (int k = 0; k < 4; ++k) add_corner_weights(sum, point_at(pt, p0 + k));
                     if constexpr (STAGE) {
-                        GRIT_STAGE_ADD(f, __builtin_amdgcn_readlane(e1, p0), __builtin_amdgcn_readlane(e2, p0),
-                                       __builtin_amdgcn_readlane(e3, p0), __builtin_amdgcn_readlane(e4, p0), W1, W2, W3, W4);
+                        staged_atomics(shead, M * D, point_at(pt, p0), sum, go_ch);
                     } else if (PACKED && !odd) {
-                        __hip_bfloat16* g1 = ghead + (size_t)__builtin_amdgcn_readlane(e1, p0) * pix_stride;
-                        __hip_bfloat16* g2 = ghead + (size_t)__builtin_amdgcn_readlane(e2, p0) * pix_stride;
-                        __hip_bfloat16* g3 = ghead + (size_t)__builtin_amdgcn_readlane(e3, p0) * pix_stride;
-                        __hip_bfloat16* g4 = ghead + (size_t)__builtin_amdgcn_readlane(e4, p0) * pix_stride;
-                        if (f & 1) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)g1, v2bf{(__bf16)(W1 * go0), (__bf16)(W1 * go1)});
-                        if (f & 2) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)g2, v2bf{(__bf16)(W2 * go0), (__bf16)(W2 * go1)});
-                        if (f & 4) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)g3, v2bf{(__bf16)(W3 * go0), (__bf16)(W3 * go1)});
-                        if (f & 8) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)g4, v2bf{(__bf16)(W4 * go0), (__bf16)(W4 * go1)});
+                        packed_atomics(ghead, pix_stride, point_at(pt, p0), sum, go0, go1);
                     }
                 }
             }
-            const int f = (2 * i + 1 < LP || !odd) ? GRIT_PICK_I(flags, i) : 0;
-            const int s1 = GRIT_PICK_I(e1, i), s2 = GRIT_PICK_I(e2, i), s3 = GRIT_PICK_I(e3, i), s4 = GRIT_PICK_I(e4, i);
-            const float lh = GRIT_PICK_F(c.lh, i), lw = GRIT_PICK_F(c.lw, i), wt = GRIT_PICK_F(pwt, i);
-            const float sW = GRIT_PICK_F(fW, i), sH = GRIT_PICK_F(fH, i);
+            const LanePoint u = point_of_half(pt, i, odd, LP);
+            const int f = u.flags;
+            const float lh = u.lh, lw = u.lw, wt = u.wt, sW = u.fW, sH = u.fH;
             const float hh = 1.f - lh, hw = 1.f - lw;
-            const float t0 = go0 * wt, t1 = go1 * wt;
             const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
             if (!merged) {
                 // the two points of this step (one per half-wave) in one cell: both halves would add to the same
                 // addresses in the same instruction -- every lane can form the sum itself (the halves hold the same
                 // channels), the lower half issues it
-                const bool pair = mergeable && 2 * i + 1 < LP &&
-                                  __builtin_amdgcn_readlane(e1, 2 * i) == __builtin_amdgcn_readlane(e1, 2 * i + 1) &&
-                                  __builtin_amdgcn_readlane(e2, 2 * i) == __builtin_amdgcn_readlane(e2, 2 * i + 1) &&
-                                  __builtin_amdgcn_readlane(e3, 2 * i) == __builtin_amdgcn_readlane(e3, 2 * i + 1) &&
-                                  __builtin_amdgcn_readlane(e4, 2 * i) == __builtin_amdgcn_readlane(e4, 2 * i + 1) &&
-                                  __builtin_amdgcn_readlane(flags, 2 * i) == __builtin_amdgcn_readlane(flags, 2 * i + 1);
+                const int pe = 2 * i, po = 2 * i + 1;  // the step's even and odd point
+                const bool pair = mergeable && po < LP && same_cells(pt, pe, po);
                 if constexpr (STAGE) {
-                    // wave-uniform weights of the step's two points (2i on the lower half, 2i + 1 on the upper)
-                    const int pa_ = 2 * i, pb_ = 2 * i + 1;
-                    const float lhA = GRIT_RLF(c.lh, pa_), lwA = GRIT_RLF(c.lw, pa_), wtA = GRIT_RLF(pwt, pa_);
-                    const float hA = (1.f - lhA) * wtA, lA = lhA * wtA;
-                    float A1 = hA * (1.f - lwA), A2 = hA * lwA, A3 = lA * (1.f - lwA), A4 = lA * lwA;
-                    const int fA = __builtin_amdgcn_readlane(flags, pa_);
-                    if (pb_ < LP) {
-                        const float lhB = GRIT_RLF(c.lh, pb_), lwB = GRIT_RLF(c.lw, pb_), wtB = GRIT_RLF(pwt, pb_);
-                        const float hB = (1.f - lhB) * wtB, lB = lhB * wtB;
-                        const float B1 = hB * (1.f - lwB), B2 = hB * lwB, B3 = lB * (1.f - lwB), B4 = lB * lwB;
-                        if (pair) {
-                            A1 += B1; A2 += B2; A3 += B3; A4 += B4;
-                        } else {
-                            GRIT_STAGE_ADD(__builtin_amdgcn_readlane(flags, pb_), __builtin_amdgcn_readlane(e1, pb_),
-                                           __builtin_amdgcn_readlane(e2, pb_), __builtin_amdgcn_readlane(e3, pb_),
-                                           __builtin_amdgcn_readlane(e4, pb_), B1, B2, B3, B4);
-                        }
+                    // wave-uniform weights of the step's two points (pe on the lower half, po on the upper)
+                    const LanePoint ue = point_at(pt, pe);
+                    CornerWeights wa = corner_weights(ue);
+                    if (po < LP) {
+                        const LanePoint uo = point_at(pt, po);
+                        const CornerWeights wb = corner_weights(uo);
+                        if (pair) add(wa, wb);
+                        else staged_atomics(shead, M * D, uo, wb, go_ch);
                     }
-                    GRIT_STAGE_ADD(fA, __builtin_amdgcn_readlane(e1, pa_), __builtin_amdgcn_readlane(e2, pa_),
-                                   __builtin_amdgcn_readlane(e3, pa_), __builtin_amdgcn_readlane(e4, pa_), A1, A2, A3, A4);
+                    staged_atomics(shead, M * D, ue, wa, go_ch);
                 }
-                float u1 = w1 * wt, u2 = w2 * wt, u3 = w3 * wt, u4 = w4 * wt;
+                CornerWeights w = {w1 * wt, w2 * wt, w3 * wt, w4 * wt};
                 bool issue = PACKED;
                 if (pair) {
                     // the other half's point: 2i + 1 for the lower half (the only one that issues)
-                    const float olh = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lh), 2 * i + 1));
-                    const float olw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.lw), 2 * i + 1));
-                    const float owt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pwt), 2 * i + 1));
-                    const float ohh = (1.f - olh) * owt, olhw = olh * owt;
-                    u1 += ohh * (1.f - olw); u2 += ohh * olw; u3 += olhw * (1.f - olw); u4 += olhw * olw;
+                    add_corner_weights(w, point_at(pt, po));
                     issue = PACKED && !odd;
                 }
-                if (PACKED && issue) {
-                    if (f & 1) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)s1 * pix_stride), v2bf{(__bf16)(u1 * go0), (__bf16)(u1 * go1)});
-                    if (f & 2) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)s2 * pix_stride), v2bf{(__bf16)(u2 * go0), (__bf16)(u2 * go1)});
-                    if (f & 4) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)s3 * pix_stride), v2bf{(__bf16)(u3 * go0), (__bf16)(u3 * go1)});
-                    if (f & 8) __builtin_amdgcn_global_atomic_fadd_v2bf16((gv2bf_ptr)(ghead + (size_t)s4 * pix_stride), v2bf{(__bf16)(u4 * go0), (__bf16)(u4 * go1)});
-                }
+                if (PACKED && issue) packed_atomics(ghead, pix_stride, u, w, go0, go1);
             }
             // clamped indices are always legal: all four were loaded, select by the validity bits
             const uint32_t q1 = (f & 1) ? rr[i][0] : 0u, q2 = (f & 2) ? rr[i][1] : 0u, q3 = (f & 4) ? rr[i][2] : 0u, q4 = (f & 8) ? rr[i][3] : 0u;
-            const float a1x = __uint_as_float(q1 << 16), a1y = __uint_as_float(q1 & 0xffff0000u);
-            const float a2x = __uint_as_float(q2 << 16), a2y = __uint_as_float(q2 & 0xffff0000u);
-            const float a3x = __uint_as_float(q3 << 16), a3y = __uint_as_float(q3 & 0xffff0000u);
-            const float a4x = __uint_as_float(q4 << 16), a4y = __uint_as_float(q4 & 0xffff0000u);
+            const float a1x = bf16_lo(q1), a1y = bf16_hi(q1);
+            const float a2x = bf16_lo(q2), a2y = bf16_hi(q2);
+            const float a3x = bf16_lo(q3), a3y = bf16_hi(q3);
+            const float a4x = bf16_lo(q4), a4y = bf16_hi(q4);
             // the two channels of this lane folded right away: go . (d/dh, d/dw, value) of the bilinear form
             const float ghx = -hw * a1x - lw * a2x + hw * a3x + lw * a4x, ghy = -hw * a1y - lw * a2y + hw * a3y + lw * a4y;
             const float gwx = -hh * a1x + hh * a2x - lh * a3x + lh * a4x, gwy = -hh * a1y + hh * a2y - lh * a3y + lh * a4y;
@@ -896,19 +961,7 @@ void msda_bwd_d64_pk(const __hip_bfloat16* __restrict__ value, const int64_t* __
             part[17 + 4 * i] = odd ? 0.f : ply;    part[17 + 4 * i + 2] = odd ? ply : 0.f;
         }
     }
-#undef GRIT_PICK_I
-#undef GRIT_PICK_F
-#undef GRIT_RLF
-#undef GRIT_STAGE_ADD
-    halve_step<64>(part, lane, 32);
-    halve_step<32>(part, lane, 16);
-    halve_step<16>(part, lane, 8);
-    halve_step<8>(part, lane, 4);
-    halve_step<4>(part, lane, 2);
-    halve_step<2>(part, lane, 1);
-    const int j = (int)(__brev((unsigned)lane) >> 26);  // index of the value this lane now owns
-    if (j < LP) grad_aw[(size_t)row * LP + j] = part[0];
-    else if (j >= 16 && j < 16 + 2 * LP) grad_loc[(size_t)row * 2 * LP + (j - 16)] = part[0];
+    store_row_grads(part, lane, row, LP, grad_loc, grad_aw);
 }
 
 // Second half of the f32-accumulating bf16 backward: every (image, pixel, head) cell whose flag is set gets its 64 staged
@@ -1177,38 +1230,105 @@ bool dims_ok(int B, int S, int M, int D, int L, int Lq, int P) {
     return rows < (1LL << 31) - 8 && (long long)L * P < (1 << 20);
 }
 
+struct Dims {
+    int B, S, M, D, L, Lq, P;
+};
+
+struct Aligned {
+    const void* p;
+    unsigned bytes;
+};
+
+// Argument check of every entry point.  Any GRIT_ERR_BAD_ARG condition (a null pointer, bad dimensions, a bad pixel stride)
+// wins over any GRIT_ERR_UNSUPPORTED one (a shape or an alignment the entry point's kernels do not take).
+//   stride_multiple: 0 for an entry point without a pixel stride, else what `pixel_stride` has to be a multiple of;
+//   max_lp: 0 for any D and L*P, else the entry point needs D == 64 and L*P <= max_lp;
+//   sorted: the shape also has to pass grit_msda_bwd_sorted_supported.
+int check_args(std::initializer_list<const void*> ptrs, const Dims& d, long pixel_stride, int stride_multiple, int max_lp,
+               std::initializer_list<Aligned> aligned, bool sorted = false) {
+    if (stride_multiple &&
+        (pixel_stride < (long)d.M * d.D || pixel_stride % stride_multiple || pixel_stride > 0x3fffffffL))
+        return GRIT_ERR_BAD_ARG;
+    for (const void* p : ptrs)
+        if (!p) return GRIT_ERR_BAD_ARG;
+    if (!dims_ok(d.B, d.S, d.M, d.D, d.L, d.Lq, d.P)) return GRIT_ERR_BAD_ARG;
+    if (sorted) {
+        const int ok = grit_msda_bwd_sorted_supported(d.B, d.S, d.M, d.L, d.Lq, d.P);
+        if (ok != GRIT_OK) return ok;
+    }
+    if (max_lp && (d.D != 64 || d.L * d.P > max_lp)) return GRIT_ERR_UNSUPPORTED;
+    for (const Aligned& a : aligned)
+        if ((uintptr_t)a.p % a.bytes) return GRIT_ERR_UNSUPPORTED;
+    return GRIT_OK;
+}
+
+// Workgroups of 256 threads that own rows_per_block rows each: 4 (a row per wave) or 16 (four rows per wave).
+struct RowGrid {
+    int nblk;
+    dim3 grid, block;
+};
+
+RowGrid row_grid(int nrows, int rows_per_block) {
+    const int nblk = (nrows + rows_per_block - 1) / rows_per_block;
+    return RowGrid{nblk, dim3(nblk), dim3(kWave * kRowsPerBlock)};
+}
+
+int launched() { return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH; }
+
+// The A/B knobs of this file, read from the environment once per process, on first use.  (GRIT_MSDA_BWD_F32ACC and
+// GRIT_MSDA_BWD_METHOD choose between the bf16 backward entry points and are read by grit_amd/ops/msda.py.)
+struct Knobs {
+    int fwd_batch;     // GRIT_MSDA_FWD_BATCH: points in flight in msda_fwd_bf16_rows4 (1, 2, 4, 8; default and anything else: 2);
+                       // 0: the row-per-wave kernel instead
+    bool interleave;   // GRIT_MSDA_BWD_INTERLEAVE=0: no image-interleaved workgroup order in msda_bwd_d64_pk
+    bool no_merge;     // GRIT_MSDA_BWD_MERGE=0: no merging of points that share a cell in msda_bwd_d64_pk
+    int value_parts;   // GRIT_MSDA_VALUE_PARTS > 0: workgroups per (image, head) in msda_bwd_value
+    bool rows1;        // GRIT_MSDA_BWD_ROWS1 != 0: grad_loc / grad_attn_w of the sorted backward by one row per wave
+};
+
+const Knobs& knobs() {
+    static const Knobs k = [] {
+        const auto env = [](const char* name, int otherwise) { return getenv(name) ? atoi(getenv(name)) : otherwise; };
+        const int batch = env("GRIT_MSDA_FWD_BATCH", 2);
+        return Knobs{(batch == 0 || batch == 1 || batch == 4 || batch == 8) ? batch : 2,
+                     env("GRIT_MSDA_BWD_INTERLEAVE", 1) != 0, env("GRIT_MSDA_BWD_MERGE", 1) == 0,
+                     env("GRIT_MSDA_VALUE_PARTS", 0), env("GRIT_MSDA_BWD_ROWS1", 0) != 0};
+    }();
+    return k;
+}
+
+// Runtime n -> template argument: calls f(std::integral_constant<int, N>) for the N of the list that equals n; false if none does.
+template <int... Ns, typename F>
+bool dispatch(int n, std::integer_sequence<int, Ns...>, F&& f) {
+    return ((n == Ns && (f(std::integral_constant<int, Ns>{}), true)) || ...);
+}
+
 template <typename T>
 int launch_fwd(const T* value, const int64_t* shapes, const int64_t* lsi, const T* loc, const T* aw,
                int B, int S, int M, int D, int L, int Lq, int P, T* out, hipStream_t st) {
-    if (!value || !shapes || !lsi || !loc || !aw || !out) return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
+    const int bad = check_args({value, shapes, lsi, loc, aw, out}, {B, S, M, D, L, Lq, P}, 0, 0, 0, {});
+    if (bad) return bad;
     const int nrows = B * Lq * M;
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    const dim3 grid(nblk), block(kWave * kRowsPerBlock);
+    const RowGrid g = row_grid(nrows, kRowsPerBlock);
     bool done = false;
     if constexpr (sizeof(T) == 4) {
         const int LP = L * P;
         const bool aligned = ((uintptr_t)value % 16 == 0) && ((uintptr_t)out % 16 == 0);
-#define GRIT_FWD_CASE(LPP_, NIT_)                                                                    \
-    hipLaunchKernelGGL((msda_fwd_vec4<LPP_, NIT_>), grid, block, 0, st, value, shapes, lsi, loc, aw, \
-                       S, M, L, Lq, P, out, nrows, nblk);                                            \
-    done = true
-        if (aligned && D == 64 && LP <= 32) {
-            const int nit = (LP + 3) / 4;
-            if (nit == 1) { GRIT_FWD_CASE(16, 1); } else if (nit == 2) { GRIT_FWD_CASE(16, 2); }
-            else if (nit == 3) { GRIT_FWD_CASE(16, 3); } else if (nit == 4) { GRIT_FWD_CASE(16, 4); }
-            else if (nit == 6) { GRIT_FWD_CASE(16, 6); } else if (nit == 8) { GRIT_FWD_CASE(16, 8); }
-        } else if (aligned && D == 32 && LP <= 32) {
-            const int nit = (LP + 7) / 8;
-            if (nit == 1) { GRIT_FWD_CASE(8, 1); } else if (nit == 2) { GRIT_FWD_CASE(8, 2); }
-            else if (nit == 3) { GRIT_FWD_CASE(8, 3); } else if (nit == 4) { GRIT_FWD_CASE(8, 4); }
-        }
-#undef GRIT_FWD_CASE
+        const auto vec4 = [&](auto lpp, auto nit) {
+            hipLaunchKernelGGL((msda_fwd_vec4<decltype(lpp)::value, decltype(nit)::value>), g.grid, g.block, 0, st, value, shapes,
+                               lsi, loc, aw, S, M, L, Lq, P, out, nrows, g.nblk);
+        };
+        if (aligned && D == 64 && LP <= 32)
+            done = dispatch((LP + 3) / 4, std::integer_sequence<int, 1, 2, 3, 4, 6, 8>{},
+                            [&](auto nit) { vec4(std::integral_constant<int, 16>{}, nit); });
+        else if (aligned && D == 32 && LP <= 32)
+            done = dispatch((LP + 7) / 8, std::integer_sequence<int, 1, 2, 3, 4>{},
+                            [&](auto nit) { vec4(std::integral_constant<int, 8>{}, nit); });
     }
     if (!done)
-        hipLaunchKernelGGL((msda_fwd_generic<T>), grid, block, 0, st, value, shapes, lsi, loc, aw,
-                           S, M, D, L, Lq, P, out, nrows, nblk);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+        hipLaunchKernelGGL((msda_fwd_generic<T>), g.grid, g.block, 0, st, value, shapes, lsi, loc, aw,
+                           S, M, D, L, Lq, P, out, nrows, g.nblk);
+    return launched();
 }
 
 template <typename VT>
@@ -1216,31 +1336,47 @@ int launch_bwd_d64(const VT* value, const int64_t* shapes, const int64_t* lsi, c
                    const VT* go, int B, int S, int M, int L, int Lq, int P, float* gv, float* gl, float* gw,
                    hipStream_t st) {
     const int nrows = B * Lq * M;
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    hipLaunchKernelGGL((msda_bwd_d64<VT>), dim3(nblk), dim3(kWave * kRowsPerBlock), 0, st, value, shapes, lsi, loc, aw, go,
-                       S, M, L, Lq, P, gv, gl, gw, nrows, nblk);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    const RowGrid g = row_grid(nrows, kRowsPerBlock);
+    hipLaunchKernelGGL((msda_bwd_d64<VT>), g.grid, g.block, 0, st, value, shapes, lsi, loc, aw, go,
+                       S, M, L, Lq, P, gv, gl, gw, nrows, g.nblk);
+    return launched();
 }
 
 template <typename T>
 int launch_bwd(const T* value, const int64_t* shapes, const int64_t* lsi, const T* loc, const T* aw,
                const T* go, int B, int S, int M, int D, int L, int Lq, int P,
                T* gv, T* gl, T* gw, hipStream_t st) {
-    if (!value || !shapes || !lsi || !loc || !aw || !go || !gv || !gl || !gw) return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    const int nrows = B * Lq * M;
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    const dim3 grid(nblk), block(kWave * kRowsPerBlock);
+    const int bad = check_args({value, shapes, lsi, loc, aw, go, gv, gl, gw}, {B, S, M, D, L, Lq, P}, 0, 0, 0, {});
+    if (bad) return bad;
     if constexpr (sizeof(T) == 4) {
         if (D == 64 && L * P <= 16) return launch_bwd_d64<float>(value, shapes, lsi, loc, aw, go, B, S, M, L, Lq, P, gv, gl, gw, st);
     }
+    const int nrows = B * Lq * M;
+    const RowGrid g = row_grid(nrows, kRowsPerBlock);
     if ((L * P) % 4 == 0)
-        hipLaunchKernelGGL((msda_bwd_generic<T, 4>), grid, block, 0, st, value, shapes, lsi, loc, aw, go,
-                           S, M, D, L, Lq, P, gv, gl, gw, nrows, nblk);
+        hipLaunchKernelGGL((msda_bwd_generic<T, 4>), g.grid, g.block, 0, st, value, shapes, lsi, loc, aw, go,
+                           S, M, D, L, Lq, P, gv, gl, gw, nrows, g.nblk);
     else
-        hipLaunchKernelGGL((msda_bwd_generic<T, 1>), grid, block, 0, st, value, shapes, lsi, loc, aw, go,
-                           S, M, D, L, Lq, P, gv, gl, gw, nrows, nblk);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+        hipLaunchKernelGGL((msda_bwd_generic<T, 1>), g.grid, g.block, 0, st, value, shapes, lsi, loc, aw, go,
+                           S, M, D, L, Lq, P, gv, gl, gw, nrows, g.nblk);
+    return launched();
+}
+
+// the row walk of the packed / staged / sorted bf16 backward
+template <Scatter MODE>
+void launch_bwd_pk(const void* value, long pixel_stride, const int64_t* shapes, const int64_t* lsi, const float* loc,
+                   const float* aw, const void* go, int B, int S, int M, int L, int Lq, int P, void* gv, float* gl, float* gw,
+                   float* stage, unsigned char* cell_flags, hipStream_t st) {
+    const int nrows = B * Lq * M;
+    const RowGrid g = row_grid(nrows, kRowsPerBlock);
+    // image-interleaved workgroup order when the rows of an image fill whole workgroups; neither it nor the merge serves a walk
+    // that scatters nothing
+    const bool scatters = MODE != Scatter::kNone;
+    const int images = (scatters && knobs().interleave && B > 1 && (Lq * M) % kRowsPerBlock == 0) ? B : 1;
+    const int no_merge = (!scatters || knobs().no_merge) ? 1 : 0;
+    hipLaunchKernelGGL(msda_bwd_d64_pk<MODE>, g.grid, g.block, 0, st, (const __hip_bfloat16*)value, shapes, lsi, loc, aw,
+                       (const __hip_bfloat16*)go, S, M, L, Lq, P, (__hip_bfloat16*)gv, gl, gw, nrows, g.nblk, images, no_merge,
+                       (int)pixel_stride, stage, cell_flags);
 }
 
 }  // namespace
@@ -1286,44 +1422,37 @@ int grit_msda_fwd_bf16(const void* value, const int64_t* spatial_shapes, const i
 int grit_msda_fwd_bf16_strided(const void* value, long pixel_stride, const int64_t* spatial_shapes,
                                const int64_t* level_start, const float* loc, const float* attn_w, int B, int S, int M,
                                int D, int L, int Lq, int P, void* out, void* stream) {
-    if (!value || !spatial_shapes || !level_start || !loc || !attn_w || !out) return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    if (pixel_stride < (long)M * D || pixel_stride % 8 || pixel_stride > 0x3fffffffL) return GRIT_ERR_BAD_ARG;
+    const int bad = check_args({value, spatial_shapes, level_start, loc, attn_w, out}, {B, S, M, D, L, Lq, P}, pixel_stride, 8, 32,
+                               {{value, 16}, {out, 16}});
+    if (bad) return bad;
     const int pix_el = (int)pixel_stride;
     const int LP = L * P;
-    if (D != 64 || LP > 32 || ((uintptr_t)value % 16) || ((uintptr_t)out % 16)) return GRIT_ERR_UNSUPPORTED;
     const int nrows = B * Lq * M;
-    if (LP <= 16 && (uint64_t)B * S * (uint64_t)pixel_stride * 2 < (1ull << 32)) {  // 4 rows per wave, 16 rows per workgroup
-        static const int batch = getenv("GRIT_MSDA_FWD_BATCH") ? atoi(getenv("GRIT_MSDA_FWD_BATCH")) : 2;
-        const int nblk16 = (nrows + 15) / 16;
-#define GRIT_ROWS4(BATCH_)                                                                                           \
-    hipLaunchKernelGGL((msda_fwd_bf16_rows4<BATCH_>), dim3(nblk16), dim3(256), 0, (hipStream_t)stream,               \
-                       (const __hip_bfloat16*)value, spatial_shapes, level_start, loc, attn_w, S, M, L, Lq, P,       \
-                       (__hip_bfloat16*)out, nrows, nblk16, pix_el)
-        if (batch == 0) goto row_per_wave;
-        if (batch == 1) GRIT_ROWS4(1); else if (batch == 4) GRIT_ROWS4(4); else if (batch == 8) GRIT_ROWS4(8); else GRIT_ROWS4(2);
-#undef GRIT_ROWS4
-        return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
-    }
-row_per_wave:
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    const dim3 grid(nblk), block(kWave * kRowsPerBlock);
-    const int nit = (LP + 7) / 8;
-#define GRIT_FWD16(NIT_)                                                                                          \
-    hipLaunchKernelGGL((msda_fwd_bf16_d64<NIT_>), grid, block, 0, (hipStream_t)stream, (const __hip_bfloat16*)value, \
-                       spatial_shapes, level_start, loc, attn_w, S, M, L, Lq, P, (__hip_bfloat16*)out, nrows, nblk, pix_el)
-    if (nit == 1) GRIT_FWD16(1); else if (nit == 2) GRIT_FWD16(2); else if (nit == 3) GRIT_FWD16(3); else GRIT_FWD16(4);
-#undef GRIT_FWD16
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    const __hip_bfloat16* v = (const __hip_bfloat16*)value;
+    __hip_bfloat16* o = (__hip_bfloat16*)out;
+    hipStream_t st = (hipStream_t)stream;
+    // four rows per wave when the byte offsets into the map fit 32 bits, else (and GRIT_MSDA_FWD_BATCH=0) one row per wave
+    const bool rows4 = knobs().fwd_batch != 0 && LP <= 16 && (uint64_t)B * S * (uint64_t)pixel_stride * 2 < (1ull << 32);
+    const RowGrid g = row_grid(nrows, rows4 ? 4 * kRowsPerBlock : kRowsPerBlock);
+    if (rows4)
+        dispatch(knobs().fwd_batch, std::integer_sequence<int, 1, 2, 4, 8>{}, [&](auto batch) {
+            hipLaunchKernelGGL((msda_fwd_bf16_rows4<decltype(batch)::value>), g.grid, g.block, 0, st, v, spatial_shapes, level_start,
+                               loc, attn_w, S, M, L, Lq, P, o, nrows, g.nblk, pix_el);
+        });
+    else
+        dispatch((LP + 7) / 8, std::integer_sequence<int, 1, 2, 3, 4>{}, [&](auto nit) {  // LP <= 32: one of them
+            hipLaunchKernelGGL((msda_fwd_bf16_d64<decltype(nit)::value>), g.grid, g.block, 0, st, v, spatial_shapes, level_start,
+                               loc, attn_w, S, M, L, Lq, P, o, nrows, g.nblk, pix_el);
+        });
+    return launched();
 }
 
 int grit_msda_bwd_bf16(const void* value, const int64_t* spatial_shapes, const int64_t* level_start, const float* loc,
                        const float* attn_w, const void* grad_out, int B, int S, int M, int D, int L, int Lq, int P,
                        float* grad_value, float* grad_loc, float* grad_attn_w, void* stream) {
-    if (!value || !spatial_shapes || !level_start || !loc || !attn_w || !grad_out || !grad_value || !grad_loc || !grad_attn_w)
-        return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    if (D != 64 || L * P > 16) return GRIT_ERR_UNSUPPORTED;
+    const int bad = check_args({value, spatial_shapes, level_start, loc, attn_w, grad_out, grad_value, grad_loc, grad_attn_w},
+                               {B, S, M, D, L, Lq, P}, 0, 0, 16, {});
+    if (bad) return bad;
     return launch_bwd_d64<__hip_bfloat16>((const __hip_bfloat16*)value, spatial_shapes, level_start, loc, attn_w,
                                             (const __hip_bfloat16*)grad_out, B, S, M, L, Lq, P, grad_value, grad_loc,
                                             grad_attn_w, (hipStream_t)stream);
@@ -1340,52 +1469,31 @@ int grit_msda_bwd_bf16acc_strided(const void* value, long pixel_stride, const in
                                   const int64_t* level_start, const float* loc, const float* attn_w, const void* grad_out,
                                   int B, int S, int M, int D, int L, int Lq, int P, void* grad_value, float* grad_loc,
                                   float* grad_attn_w, void* stream) {
-    if (pixel_stride < (long)M * D || pixel_stride % 2 || pixel_stride > 0x3fffffffL) return GRIT_ERR_BAD_ARG;
-    if (!value || !spatial_shapes || !level_start || !loc || !attn_w || !grad_out || !grad_value || !grad_loc || !grad_attn_w)
-        return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    if (D != 64 || L * P > 16 || ((uintptr_t)value % 4) || ((uintptr_t)grad_out % 4) || ((uintptr_t)grad_value % 4))
-        return GRIT_ERR_UNSUPPORTED;
-    const int nrows = B * Lq * M;
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    // image-interleaved workgroup order when the rows of an image fill whole workgroups (GRIT_MSDA_BWD_INTERLEAVE=0: off)
-    static const bool interleave = !(getenv("GRIT_MSDA_BWD_INTERLEAVE") && atoi(getenv("GRIT_MSDA_BWD_INTERLEAVE")) == 0);
-    const int images = (interleave && B > 1 && (Lq * M) % kRowsPerBlock == 0) ? B : 1;
-    static const bool no_merge = getenv("GRIT_MSDA_BWD_MERGE") && atoi(getenv("GRIT_MSDA_BWD_MERGE")) == 0;  // A/B knob
-    hipLaunchKernelGGL(msda_bwd_d64_pk<0>, dim3(nblk), dim3(kWave * kRowsPerBlock), 0, (hipStream_t)stream,
-                       (const __hip_bfloat16*)value, spatial_shapes, level_start, loc, attn_w, (const __hip_bfloat16*)grad_out,
-                       S, M, L, Lq, P, (__hip_bfloat16*)grad_value, grad_loc, grad_attn_w, nrows, nblk, images, no_merge ? 1 : 0,
-                       (int)pixel_stride, (float*)nullptr, (unsigned char*)nullptr);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    const int bad = check_args({value, spatial_shapes, level_start, loc, attn_w, grad_out, grad_value, grad_loc, grad_attn_w},
+                               {B, S, M, D, L, Lq, P}, pixel_stride, 2, 16, {{value, 4}, {grad_out, 4}, {grad_value, 4}});
+    if (bad) return bad;
+    launch_bwd_pk<Scatter::kPacked>(value, pixel_stride, spatial_shapes, level_start, loc, attn_w, grad_out, B, S, M, L, Lq, P,
+                                    grad_value, grad_loc, grad_attn_w, nullptr, nullptr, (hipStream_t)stream);
+    return launched();
 }
 
 int grit_msda_bwd_bf16_staged(const void* value, long pixel_stride, const int64_t* spatial_shapes,
                               const int64_t* level_start, const float* loc, const float* attn_w, const void* grad_out,
                               int B, int S, int M, int D, int L, int Lq, int P, float* stage, unsigned char* cell_flags,
                               void* grad_value, float* grad_loc, float* grad_attn_w, void* stream) {
-    if (pixel_stride < (long)M * D || pixel_stride % 2 || pixel_stride > 0x3fffffffL) return GRIT_ERR_BAD_ARG;
-    if (!value || !spatial_shapes || !level_start || !loc || !attn_w || !grad_out || !grad_value || !grad_loc || !grad_attn_w ||
-        !stage || !cell_flags)
-        return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    if (D != 64 || L * P > 16 || ((uintptr_t)value % 4) || ((uintptr_t)grad_out % 4) || ((uintptr_t)grad_value % 2) ||
-        ((uintptr_t)stage % 4))
-        return GRIT_ERR_UNSUPPORTED;
-    const int nrows = B * Lq * M;
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    static const bool interleave = !(getenv("GRIT_MSDA_BWD_INTERLEAVE") && atoi(getenv("GRIT_MSDA_BWD_INTERLEAVE")) == 0);
-    const int images = (interleave && B > 1 && (Lq * M) % kRowsPerBlock == 0) ? B : 1;
-    static const bool no_merge = getenv("GRIT_MSDA_BWD_MERGE") && atoi(getenv("GRIT_MSDA_BWD_MERGE")) == 0;
-    hipLaunchKernelGGL(msda_bwd_d64_pk<1>, dim3(nblk), dim3(kWave * kRowsPerBlock), 0, (hipStream_t)stream,
-                       (const __hip_bfloat16*)value, spatial_shapes, level_start, loc, attn_w, (const __hip_bfloat16*)grad_out,
-                       S, M, L, Lq, P, (__hip_bfloat16*)nullptr, grad_loc, grad_attn_w, nrows, nblk, images, no_merge ? 1 : 0,
-                       (int)pixel_stride, stage, cell_flags);
-    if (hipGetLastError() != hipSuccess) return GRIT_ERR_LAUNCH;
+    const int bad = check_args({value, spatial_shapes, level_start, loc, attn_w, grad_out, grad_value, grad_loc, grad_attn_w,
+                                stage, cell_flags},
+                               {B, S, M, D, L, Lq, P}, pixel_stride, 2, 16,
+                               {{value, 4}, {grad_out, 4}, {grad_value, 2}, {stage, 4}});
+    if (bad) return bad;
+    launch_bwd_pk<Scatter::kStaged>(value, pixel_stride, spatial_shapes, level_start, loc, attn_w, grad_out, B, S, M, L, Lq, P,
+                                    nullptr, grad_loc, grad_attn_w, stage, cell_flags, (hipStream_t)stream);
+    if (launched() != GRIT_OK) return GRIT_ERR_LAUNCH;
     const long ncells = (long)B * S * M;
     const long nwaves = (ncells + 63) / 64;
     hipLaunchKernelGGL(msda_stage_flush, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, stage, cell_flags,
                        (__hip_bfloat16*)grad_value, ncells, S, M, (int)pixel_stride);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    return launched();
 }
 
 int grit_msda_bwd_sorted_supported(int B, int S, int M, int L, int Lq, int P) {
@@ -1399,14 +1507,10 @@ int grit_msda_bwd_bf16_sorted(const void* value, long pixel_stride, const int64_
                               const int64_t* level_start, const float* loc, const float* attn_w, const void* grad_out,
                               int B, int S, int M, int D, int L, int Lq, int P, void* grad_value, float* grad_loc,
                               float* grad_attn_w, void* stream) {
-    if (pixel_stride < (long)M * D || pixel_stride % 8 || pixel_stride > 0x3fffffffL) return GRIT_ERR_BAD_ARG;
-    if (!value || !spatial_shapes || !level_start || !loc || !attn_w || !grad_out || !grad_value || !grad_loc || !grad_attn_w)
-        return GRIT_ERR_BAD_ARG;
-    if (!dims_ok(B, S, M, D, L, Lq, P)) return GRIT_ERR_BAD_ARG;
-    const int ok = grit_msda_bwd_sorted_supported(B, S, M, L, Lq, P);
-    if (ok != GRIT_OK) return ok;
-    if (D != 64 || L * P > 16 || ((uintptr_t)value % 4) || ((uintptr_t)grad_out % 16) || ((uintptr_t)grad_value % 16))
-        return GRIT_ERR_UNSUPPORTED;
+    const int bad = check_args({value, spatial_shapes, level_start, loc, attn_w, grad_out, grad_value, grad_loc, grad_attn_w},
+                               {B, S, M, D, L, Lq, P}, pixel_stride, 8, 16, {{value, 4}, {grad_out, 16}, {grad_value, 16}},
+                               /*sorted=*/true);
+    if (bad) return bad;
     hipStream_t st = (hipStream_t)stream;
     static grit_detail::PerDevice<bool> lds_attr_set_pd; bool& lds_attr_set = lds_attr_set_pd();  // idempotent attribute
     if (!lds_attr_set) {
@@ -1415,28 +1519,24 @@ int grit_msda_bwd_bf16_sorted(const void* value, long pixel_stride, const int64_
         lds_attr_set = true;
     }
     // fewer (image, head) segments than CUs: several workgroups per segment (GRIT_MSDA_VALUE_PARTS overrides: A/B)
-    static const int parts_env = getenv("GRIT_MSDA_VALUE_PARTS") ? atoi(getenv("GRIT_MSDA_VALUE_PARTS")) : 0;
-    int parts = parts_env > 0 ? parts_env : 256 / (B * M);
+    int parts = knobs().value_parts > 0 ? knobs().value_parts : 256 / (B * M);
     parts = parts < 1 ? 1 : (parts > 8 ? 8 : parts);
     hipLaunchKernelGGL(msda_bwd_value, dim3(B * M * parts), dim3(kValueThreads), value_lds_bytes(S, L, Lq, P), st, spatial_shapes,
                        level_start, loc, attn_w, (const __hip_bfloat16*)grad_out, (__hip_bfloat16*)grad_value, S, M, L, Lq, P,
                        (int)pixel_stride, parts);
-    if (hipGetLastError() != hipSuccess) return GRIT_ERR_LAUNCH;
-    const int nrows = B * Lq * M;
-    static const bool rows1 = getenv("GRIT_MSDA_BWD_ROWS1") && atoi(getenv("GRIT_MSDA_BWD_ROWS1")) != 0;  // A/B: one row per wave
-    if (!rows1 && (long)B * S * pixel_stride * 2 < (1LL << 32) && (uintptr_t)value % 16 == 0) {
-        const int nblk16 = (nrows + 15) / 16;
-        hipLaunchKernelGGL(msda_bwd_rows4<2>, dim3(nblk16), dim3(256), 0, st, (const __hip_bfloat16*)value, spatial_shapes,
+    if (launched() != GRIT_OK) return GRIT_ERR_LAUNCH;
+    // grad_loc / grad_attn_w: four rows per wave when the byte offsets into the map fit 32 bits, else one row per wave
+    if (!knobs().rows1 && (long)B * S * pixel_stride * 2 < (1LL << 32) && (uintptr_t)value % 16 == 0) {
+        const int nrows = B * Lq * M;
+        const RowGrid g = row_grid(nrows, 4 * kRowsPerBlock);
+        hipLaunchKernelGGL(msda_bwd_rows4<2>, g.grid, g.block, 0, st, (const __hip_bfloat16*)value, spatial_shapes,
                            level_start, loc, attn_w, (const __hip_bfloat16*)grad_out, S, M, L, Lq, P, grad_loc, grad_attn_w,
-                           nrows, nblk16, (int)pixel_stride);
-        return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+                           nrows, g.nblk, (int)pixel_stride);
+    } else {
+        launch_bwd_pk<Scatter::kNone>(value, pixel_stride, spatial_shapes, level_start, loc, attn_w, grad_out, B, S, M, L, Lq, P,
+                                      nullptr, grad_loc, grad_attn_w, nullptr, nullptr, st);
     }
-    const int nblk = (nrows + kRowsPerBlock - 1) / kRowsPerBlock;
-    hipLaunchKernelGGL(msda_bwd_d64_pk<2>, dim3(nblk), dim3(kWave * kRowsPerBlock), 0, st, (const __hip_bfloat16*)value,
-                       spatial_shapes, level_start, loc, attn_w, (const __hip_bfloat16*)grad_out, S, M, L, Lq, P,
-                       (__hip_bfloat16*)nullptr, grad_loc, grad_attn_w, nrows, nblk, 1, 1, (int)pixel_stride, (float*)nullptr,
-                       (unsigned char*)nullptr);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    return launched();
 }
 
 }  // extern "C"

@@ -59,17 +59,6 @@ def _staging(device, B, S, M):
     return ent
 
 
-def _bwd_staged(value_ptr, pixel_stride, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P, gv_ptr, gl, ga, device):
-    ent = _staging(device, B, S, M)
-    ent[2] = True
-    with _lib.device_guard(device), _Timed("bwd_bf16", _algorithmic_bytes("bwd", B, S, M, D, L, Lq, P, 2, 4, 4)):
-        st = _lib.load().grit_msda_bwd_bf16_staged(value_ptr, pixel_stride, _ptr(shapes), _ptr(lsi), _ptr(loc), _ptr(aw), _ptr(go),
-                                                   B, S, M, D, L, Lq, P, _ptr(ent[0]), _ptr(ent[1]), gv_ptr, _ptr(gl), _ptr(ga),
-                                                   _lib.current_stream_ptr())
-    _lib.check(st, "grit_msda_bwd_bf16_staged")
-    ent[2] = False
-
-
 def sorted_applies(B, S, M, L, Lq, P):
     """True when the gather-form backward handles the shape (one (image, head) problem must fit the LDS of a CU)."""
     return F32_METHOD == "sorted" and _lib.load().grit_msda_bwd_sorted_supported(B, S, M, L, Lq, P) == 0
@@ -78,14 +67,50 @@ def sorted_applies(B, S, M, L, Lq, P):
 LAST_BWD_SHAPE = None  # (B, S, M, L, Lq, P) of the last gather-form backward (bench.py prices its bytes with it)
 
 
-def _bwd_sorted(value_ptr, pixel_stride, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P, gv_ptr, gl, ga, device):
-    """Value gradient in gather form; writes EVERY cell of the [B, S, M, 64] slice behind gv_ptr."""
+def _bwd_method(B, S, M, L, Lq, P):
+    """Which bf16 backward serves the shape: "packed" (bf16 atomics), "sorted" (gather form; writes EVERY cell of the gradient
+    slice, so the buffer needs no fill) or "staged" (f32 atomics + flush; also where the sorted form does not apply)."""
+    if not F32_ACCUMULATE:
+        return "packed"
+    return "sorted" if sorted_applies(B, S, M, L, Lq, P) else "staged"
+
+
+def _fwd_bf16(value_ptr, pixel_stride, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, device):
+    """Forward on a bf16 map [B, S, M, 64] whose pixels lie `pixel_stride` elements apart (M*D: dense); loc / aw float32."""
+    out = torch.empty((B, Lq, M * D), dtype=torch.bfloat16, device=device)
+    geometry = (loc, shapes, lsi, B, S, M, 2) if PROFILE_RECORD_GEOMETRY else None
+    with _lib.device_guard(device), _Timed("fwd_bf16", _algorithmic_bytes("fwd", B, S, M, D, L, Lq, P, 2, 4), geometry):
+        st = _lib.load().grit_msda_fwd_bf16_strided(value_ptr, pixel_stride, _ptr(shapes), _ptr(lsi), _ptr(loc), _ptr(aw),
+                                                    B, S, M, D, L, Lq, P, _ptr(out), _lib.current_stream_ptr())
+    _lib.check(st, "grit_msda_fwd_bf16_strided")
+    return out
+
+
+def _bwd_bf16(method, value_ptr, pixel_stride, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P, gv_ptr, gl, ga, device):
+    """Backward on a bf16 map with pixels `pixel_stride` elements apart, by _bwd_method's `method`.  The gradient slice behind
+    gv_ptr has the map's layout; "packed" and "staged" add into it (it arrives zeroed), "sorted" writes all of it."""
     global LAST_BWD_SHAPE
-    LAST_BWD_SHAPE = (B, S, M, L, Lq, P)
-    with _lib.device_guard(device), _Timed("bwd_bf16", _algorithmic_bytes("bwd", B, S, M, D, L, Lq, P, 2, 4, 2)):
-        st = _lib.load().grit_msda_bwd_bf16_sorted(value_ptr, pixel_stride, _ptr(shapes), _ptr(lsi), _ptr(loc), _ptr(aw), _ptr(go),
-                                                   B, S, M, D, L, Lq, P, gv_ptr, _ptr(gl), _ptr(ga), _lib.current_stream_ptr())
-    _lib.check(st, "grit_msda_bwd_bf16_sorted")
+    lib = _lib.load()
+    args = (value_ptr, pixel_stride, _ptr(shapes), _ptr(lsi), _ptr(loc), _ptr(aw), _ptr(go), B, S, M, D, L, Lq, P)
+    grad_esize = 4 if method == "staged" else 2  # what the kernel accumulates grad_value in
+    if method == "staged":
+        ent = _staging(device, B, S, M)
+        ent[2] = True
+    with _lib.device_guard(device), _Timed("bwd_bf16", _algorithmic_bytes("bwd", B, S, M, D, L, Lq, P, 2, 4, grad_esize)):
+        stream = _lib.current_stream_ptr()  # of `device`: taken inside the guard
+        if method == "sorted":
+            LAST_BWD_SHAPE = (B, S, M, L, Lq, P)
+            name, st = "grit_msda_bwd_bf16_sorted", lib.grit_msda_bwd_bf16_sorted(*args, gv_ptr, _ptr(gl), _ptr(ga), stream)
+        elif method == "staged":
+            name, st = "grit_msda_bwd_bf16_staged", lib.grit_msda_bwd_bf16_staged(*args, _ptr(ent[0]), _ptr(ent[1]), gv_ptr,
+                                                                                   _ptr(gl), _ptr(ga), stream)
+        else:
+            # value gradient accumulated in bf16 by packed atomics (two channels per memory-side atomic: the f32-atomic rate
+            # is what bounds the f32 kernel) -- the rounding behaviour of torch's own bf16 scatter / grid_sample backward
+            name, st = "grit_msda_bwd_bf16acc_strided", lib.grit_msda_bwd_bf16acc_strided(*args, gv_ptr, _ptr(gl), _ptr(ga), stream)
+    _lib.check(st, name)
+    if method == "staged":
+        ent[2] = False
 
 
 _ptr = _lib.ptr
@@ -178,14 +203,8 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     if LOC_OVERRIDE is not None:
         sampling_loc = LOC_OVERRIDE(sampling_loc).to(sampling_loc.dtype).contiguous()
     if _bf16_fast_path(value, D, L, P):  # value map stays bf16: no fp32 staging copy
-        loc, aw = sampling_loc.float(), attn_weight.float()
-        out = torch.empty((B, Lq, M * D), dtype=torch.bfloat16, device=value.device)
-        geometry = (loc, spatial_shapes, level_start_index, B, S, M, 2) if PROFILE_RECORD_GEOMETRY else None
-        with _lib.device_guard(value.device), _Timed("fwd_bf16", _algorithmic_bytes("fwd", B, S, M, D, L, Lq, P, 2, 4), geometry):
-            st = _lib.load().grit_msda_fwd_bf16(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(loc),
-                                                _ptr(aw), B, S, M, D, L, Lq, P, _ptr(out), _lib.current_stream_ptr())
-        _lib.check(st, "grit_msda_fwd_bf16")
-        return out
+        return _fwd_bf16(_ptr(value), M * D, spatial_shapes, level_start_index, sampling_loc.float(), attn_weight.float(),
+                         B, S, M, D, L, Lq, P, value.device)
     cdt = _compute_dtype(value)
     v, loc, aw = value.to(cdt), sampling_loc.to(cdt), attn_weight.to(cdt)
     out = torch.empty((B, Lq, M * D), dtype=cdt, device=value.device)
@@ -202,31 +221,15 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
                             im2col_step=64):
     B, S, M, D, L, Lq, P = _check_inputs(value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     _lib.require_device(grad_output)
-    if _bf16_fast_path(value, D, L, P) and not F32_ACCUMULATE:
-        # value gradient accumulated in bf16 by packed atomics (two channels per memory-side atomic: the f32-atomic rate
-        # is what bounds this kernel) -- the rounding behaviour of torch's own bf16 scatter / grid_sample backward
-        loc, aw = sampling_loc.float(), attn_weight.float()
-        go = grad_output.to(torch.bfloat16).contiguous()
-        gv = torch.zeros(value.shape, dtype=torch.bfloat16, device=value.device)
-        gl, ga = torch.empty_like(loc), torch.empty_like(aw)
-        with _lib.device_guard(value.device), _Timed("bwd_bf16", _algorithmic_bytes("bwd", B, S, M, D, L, Lq, P, 2, 4, 2)):
-            st = _lib.load().grit_msda_bwd_bf16acc(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(loc),
-                                                   _ptr(aw), _ptr(go), B, S, M, D, L, Lq, P, _ptr(gv), _ptr(gl), _ptr(ga),
-                                                   _lib.current_stream_ptr())
-        _lib.check(st, "grit_msda_bwd_bf16acc")
-        return [gv, gl.to(sampling_loc.dtype), ga.to(attn_weight.dtype)]
     if _bf16_fast_path(value, D, L, P):
         loc, aw = sampling_loc.float(), attn_weight.float()
         go = grad_output.to(torch.bfloat16).contiguous()
         gl, ga = torch.empty_like(loc), torch.empty_like(aw)
-        if sorted_applies(B, S, M, L, Lq, P):
-            gv = torch.empty(value.shape, dtype=torch.bfloat16, device=value.device)  # every cell is written
-            _bwd_sorted(_ptr(value), M * D, spatial_shapes, level_start_index, loc.contiguous(), aw.contiguous(), go,
-                        B, S, M, D, L, Lq, P, _ptr(gv), gl, ga, value.device)
-        else:
-            gv = torch.zeros(value.shape, dtype=torch.bfloat16, device=value.device)
-            _bwd_staged(_ptr(value), M * D, spatial_shapes, level_start_index, loc, aw, go, B, S, M, D, L, Lq, P, _ptr(gv), gl,
-                        ga, value.device)
+        method = _bwd_method(B, S, M, L, Lq, P)
+        alloc = torch.empty if method == "sorted" else torch.zeros  # sorted: every cell is written
+        gv = alloc(value.shape, dtype=torch.bfloat16, device=value.device)
+        _bwd_bf16(method, _ptr(value), M * D, spatial_shapes, level_start_index, loc, aw, go, B, S, M, D, L, Lq, P, _ptr(gv),
+                  gl, ga, value.device)
         return [gv, gl.to(sampling_loc.dtype), ga.to(attn_weight.dtype)]
     cdt = _compute_dtype(value)
     v, loc, aw = value.to(cdt), sampling_loc.to(cdt), attn_weight.to(cdt)
@@ -270,13 +273,7 @@ class _StackedMSDAFn(Function):
         loc, aw = loc.float().contiguous(), aw.float().contiguous()
         if LOC_OVERRIDE is not None:
             loc = LOC_OVERRIDE(loc).float().contiguous()
-        out = torch.empty((B, Lq, M * D), dtype=torch.bfloat16, device=stacked.device)
-        geometry = (loc, shapes, lsi, B, S, M, 2) if PROFILE_RECORD_GEOMETRY else None
-        with _lib.device_guard(stacked.device), _Timed("fwd_bf16", _algorithmic_bytes("fwd", B, S, M, D, L, Lq, P, 2, 4), geometry):
-            st = _lib.load().grit_msda_fwd_bf16_strided(maps.layer_ptr(stacked, layer), n * M * D, _ptr(shapes), _ptr(lsi),
-                                                        _ptr(loc), _ptr(aw), B, S, M, D, L, Lq, P, _ptr(out),
-                                                        _lib.current_stream_ptr())
-        _lib.check(st, "grit_msda_fwd_bf16_strided")
+        out = _fwd_bf16(maps.layer_ptr(stacked, layer), n * M * D, shapes, lsi, loc, aw, B, S, M, D, L, Lq, P, stacked.device)
         ctx.save_for_backward(stacked, shapes, lsi, loc, aw)
         ctx.maps, ctx.layer = maps, layer
         maps.pending += 1
@@ -290,27 +287,16 @@ class _StackedMSDAFn(Function):
         maps, layer = ctx.maps, ctx.layer
         B, S, n, M, D = stacked.shape
         _, Lq, _, L, P, _ = loc.shape
-        use_sorted = F32_ACCUMULATE and sorted_applies(B, S, M, L, Lq, P)
+        method = _bwd_method(B, S, M, L, Lq, P)
         if maps.grad is None:
             # sorted path: every layer's kernel writes its whole slice, so the buffer needs no fill -- provided every slice has
             # a sampling node waiting (all layers of the decoder ran); otherwise one fill for all layers
-            every_slice = use_sorted and maps.layers_seen == set(range(n)) and maps.pending == n
+            every_slice = method == "sorted" and maps.layers_seen == set(range(n)) and maps.pending == n
             maps.grad = torch.empty_like(stacked) if every_slice else torch.zeros_like(stacked)
         go = grad_output.to(torch.bfloat16).contiguous()
         gl, ga = torch.empty_like(loc), torch.empty_like(aw)
-        if use_sorted:
-            _bwd_sorted(maps.layer_ptr(stacked, layer), n * M * D, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P,
-                        maps.layer_ptr(maps.grad, layer), gl, ga, stacked.device)
-        elif F32_ACCUMULATE:
-            _bwd_staged(maps.layer_ptr(stacked, layer), n * M * D, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P,
-                        maps.layer_ptr(maps.grad, layer), gl, ga, stacked.device)
-        else:
-            with _lib.device_guard(stacked.device), _Timed("bwd_bf16", _algorithmic_bytes("bwd", B, S, M, D, L, Lq, P, 2, 4, 2)):
-                st = _lib.load().grit_msda_bwd_bf16acc_strided(maps.layer_ptr(stacked, layer), n * M * D, _ptr(shapes), _ptr(lsi),
-                                                               _ptr(loc), _ptr(aw), _ptr(go), B, S, M, D, L, Lq, P,
-                                                               maps.layer_ptr(maps.grad, layer), _ptr(gl), _ptr(ga),
-                                                               _lib.current_stream_ptr())
-            _lib.check(st, "grit_msda_bwd_bf16acc_strided")
+        _bwd_bf16(method, maps.layer_ptr(stacked, layer), n * M * D, shapes, lsi, loc, aw, go, B, S, M, D, L, Lq, P,
+                  maps.layer_ptr(maps.grad, layer), gl, ga, stacked.device)
         maps.pending -= 1
         gstacked = None
         if maps.pending == 0:  # every layer has added its part

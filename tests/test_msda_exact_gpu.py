@@ -18,7 +18,7 @@ grit_msda_bwd_bf16_sorted; LP = L*P, configurations by their name in tests/msda_
     one point in last round  "                                LP = 9, 17, 25                              test_f32_op_exact[d32_lp9], [d32_lp17], [d32_lp25]
   msda_fwd_generic<float>    "                                D not in {32, 64}                           test_f32_op_exact[d1_lp6], [d7_lp6], [d130_lp5]
   msda_fwd_generic<double>   op, f64 (grit_msda_fwd_f64)      always                                      test_f64_op_exact[d64_lp16], [d7_lp6]
-  msda_fwd_bf16_rows4<2>     op, bf16 (grit_msda_fwd_bf16)    LP <= 16, map below 4 GB, no environment    test_bf16_forward_op[d64_lp4 | lp6 | lp8 | lp9 | lp12 | lp16 | lp16_1row | lp16_100]
+  msda_fwd_bf16_rows4<2>     op, bf16 (.._fwd_bf16_strided)   LP <= 16, map below 4 GB, no environment    test_bf16_forward_op[d64_lp4 | lp6 | lp8 | lp9 | lp12 | lp16 | lp16_1row | lp16_100]
   msda_fwd_bf16_rows4<2>     grit_msda_fwd_bf16_strided       same, pixel_stride = 3 M D                  test_bf16_forward_strided_slice
   msda_fwd_bf16_rows4<1|4|8> op, bf16, child process          GRIT_MSDA_FWD_BATCH = 1, 4, 8               test_bf16_forward_batch_variants[1], [4], [8]
   msda_fwd_bf16_d64<1>, <2>  op, bf16, child process          GRIT_MSDA_FWD_BATCH = 0, (LP + 7) / 8       test_bf16_forward_batch_variants[0] (LP = 6; 9 and 16)
@@ -30,15 +30,15 @@ grit_msda_bwd_bf16_sorted; LP = L*P, configurations by their name in tests/msda_
   msda_bwd_generic<float, 1> "                                otherwise, LP % 4 != 0                      test_f32_op_exact[d7_lp6], [d130_lp5], [d1_lp6], [d64_lp17]
   msda_bwd_generic<double,.> op, f64 (grit_msda_bwd_f64)      always (4: LP = 16, 1: LP = 6)              test_f64_op_exact[d64_lp16], [d7_lp6]
   msda_bwd_d64<bf16>         grit_msda_bwd_bf16               D = 64, LP <= 16                            test_bf16_backward_forms[dense-*]
-  msda_bwd_d64_pk<1> + flush grit_msda_bwd_bf16_staged        D = 64, LP <= 16                            test_bf16_backward_forms[staged-*]
+  ..d64_pk<kStaged> + flush  grit_msda_bwd_bf16_staged        D = 64, LP <= 16                            test_bf16_backward_forms[staged-*]
     merged / pair branch     "                                P = 4, LP = 16, points share a cell         test_bf16_backward_forms[staged-d64_cluster]
     neither branch           "                                P = 2                                       test_bf16_backward_forms[staged-d64_lp8_p2]
     image-interleaved order  "                                B > 1, (Lq M) % 4 == 0                      [..-d64_lp8], [..-d64_cluster], [..-d64_lp16_100]; not: [..-d64_lp16]
-  msda_bwd_d64_pk<0>         grit_msda_bwd_bf16acc            D = 64, LP <= 16 (coarse lattice)           test_bf16_backward_forms[packed-pk_*]
+  msda_bwd_d64_pk<kPacked>   grit_msda_bwd_bf16acc            D = 64, LP <= 16 (coarse lattice)           test_bf16_backward_forms[packed-pk_*]
     merged / pair branch     "                                P = 4, LP = 16, points share a cell         test_bf16_backward_forms[packed-pk_cluster]
     neither branch           "                                P = 2                                       test_bf16_backward_forms[packed-pk_lp8_p2]
   msda_bwd_value + rows4<2>  grit_msda_bwd_bf16_sorted        value 16-byte aligned, map below 4 GB       test_bf16_backward_forms[sorted-*]
-  msda_bwd_d64_pk<2>         "                                value 4 bytes off 16-byte alignment         test_sorted_unaligned_value_takes_the_row_walk
+  msda_bwd_d64_pk<kNone>     "                                value 4 bytes off 16-byte alignment         test_sorted_unaligned_value_takes_the_row_walk
   msda_bwd_value, parts = n  "                                parts = clamp(256 / (B M), 1, 8)            test_sorted_value_partitions[val_parts1 | 2 | 3 | 4 | 5 | 8]
     16 waves all own tiles   "                                S = 4160, parts = 1                         test_sorted_value_partitions[val_big]
     one tile, 128 waves      "                                S = 3, parts = 8                            test_sorted_value_partitions[val_s3]
