@@ -47,6 +47,12 @@ _DEFAULTS = {
         # diverse beam search of evaluation and inference: beam_groups groups of beam_size / beam_groups beams searched in turn, a
         # group paying beam_diversity per earlier choice of the same word at a step (1 group: the plain search, as in the reference)
         beam_groups=1, beam_diversity=0.0,
+        # consensus (minimum-Bayes-risk) reranking of evaluation under CIDEr-D (grit_amd/ops/consensus.py): of consensus_candidates
+        # candidates per image the one that agrees most with the others is scored (0 or 1: off, hypothesis 0 as in the reference).
+        # consensus_decode 'beam': the N best final hypotheses of the search configured above (N <= beam_size); 'sample': N samples
+        # at consensus_temperature / consensus_top_k / consensus_top_p from consensus_seed (None: torch's device generator)
+        consensus_candidates=0, consensus_decode='beam', consensus_temperature=1.0, consensus_top_k=0, consensus_top_p=1.0,
+        consensus_seed=None,
         dropout=0.2, attn_dropout=0.2, vocab_size=10201, max_len=54, pad_idx=1, bos_idx=2, eos_idx=3, d_model=512,
         n_heads=8, grid_net=dict(n_memories=1, n_layers=3), cap_generator=dict(decoder_name='parallel', n_layers=3),
         detector=dict(checkpoint='', d_model=512, dim_feedforward=1024, num_heads=8, num_layers=6, num_levels=4,
@@ -79,6 +85,21 @@ def beam_groups(config):
     written before they existed gives the defaults (one group: the plain search)."""
     m = config.model
     return dict(num_groups=getattr(m, 'beam_groups', 1), diversity=getattr(m, 'beam_diversity', 0.0))
+
+
+def consensus_options(config):
+    """The model.consensus_* keys as a dictionary: candidates (0: off; 1 counts as off), decode ('beam' / 'sample') and the sampling
+    keywords of Transformer.forward for 'sample'.  A config written before the keys existed is off."""
+    m = config.model
+    n = int(getattr(m, 'consensus_candidates', 0) or 0)
+    decode = getattr(m, 'consensus_decode', 'beam')
+    if n < 0:
+        raise ValueError("model.consensus_candidates must be >= 0, not %r" % (n,))
+    if decode not in ('beam', 'sample'):
+        raise ValueError("model.consensus_decode must be 'beam' or 'sample', not %r" % (decode,))
+    return dict(candidates=n if n > 1 else 0, decode=decode,
+                sample=dict(temperature=getattr(m, 'consensus_temperature', 1.0), top_k=getattr(m, 'consensus_top_k', 0),
+                            top_p=getattr(m, 'consensus_top_p', 1.0), seed=getattr(m, 'consensus_seed', None)))
 
 
 def default_config(**overrides):

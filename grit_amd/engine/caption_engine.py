@@ -270,8 +270,62 @@ def _split_scorer(dataloader, caption_lists, text_field, device):
 _SPLIT_SCORERS = {}
 
 
+def consensus_reranker(consensus, text_field):
+    """What evaluate_metrics(consensus=...) takes, as `rerank(tokens [B, n, T], log_probs) -> Consensus`: a ready reranker (an
+    object with a `consensus` method, such as a DeviceCider) is used as it is; a `Cider` with corpus statistics gets its device
+    tables at the first call, on the device the tokens come from, and keeps them on the Cider object as the device reward does
+    (one DeviceCider serves both).  A Cider without statistics is refused here, before anything is decoded."""
+    if hasattr(consensus, 'consensus'):
+        return consensus.consensus
+    if getattr(consensus, 'doc_frequency', None) is None:
+        raise ValueError("consensus reranking needs a Cider built with corpus statistics (Cider(gts)), or a ready reranker")
+    if text_field is None:
+        raise ValueError("consensus reranking with a Cider needs a text_field (its vocabulary)")
+    vocab = getattr(text_field, 'vocab', None)
+    itos = vocab.itos if vocab is not None and hasattr(vocab, 'itos') else text_field.itos
+    eos_token = getattr(text_field, 'eos_token', '<eos>')
+    holder = consensus.__dict__.setdefault('_device_scorers', {})
+    vocab_key = (eos_token, hash(tuple(itos)))
+
+    def rerank(tokens, log_probs=None, **kw):
+        from grit_amd import lib
+        from grit_amd.ops.cider import DeviceCider
+        lib.require_device(tokens)
+        tables = holder.get((tokens.device, vocab_key))
+        if tables is None:
+            tables = holder[(tokens.device, vocab_key)] = DeviceCider(consensus, itos, eos_token=eos_token, device=tokens.device)
+        return tables.consensus(tokens, log_probs, **kw)
+
+    return rerank
+
+
+def decode_consensus(model, samples, config, reranker):
+    """Decode model.consensus_candidates candidates per image as model.consensus_decode says ('beam': the N best final hypotheses
+    of the configured search, constraints and groups honoured; 'sample': N samples) and keep the one that `reranker(tokens,
+    log_probs)` chooses (DeviceCider.consensus, or consensus_reranker(...)).  Returns (tokens [B, 1, T], log_probs [B, 1, T]).
+    An Ensemble decodes 'beam' only and raises for 'sample', as it does anywhere."""
+    from grit_amd.config import consensus_options
+    opt = consensus_options(config)
+    n = opt['candidates']
+    if n < 2:
+        raise ValueError("decode_consensus needs model.consensus_candidates > 1")
+    common = dict(seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx)
+    with torch.no_grad():
+        if opt['decode'] == 'sample':
+            tokens, log_probs = model(samples, beam_size=n, out_size=n, decode='sample', **opt['sample'], **common)
+        else:
+            if n > config.model.beam_size:
+                raise ValueError("model.consensus_candidates = %d exceeds model.beam_size = %d: a beam search has no more final "
+                                 "hypotheses than beams" % (n, config.model.beam_size))
+            tokens, log_probs = model(samples, beam_size=config.model.beam_size, out_size=n, return_probs=False,
+                                      **beam_constraints(config), **beam_groups(config), **common)
+        chosen = reranker(tokens, log_probs)
+    return chosen.tokens, chosen.log_probs
+
+
 def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='test', config=None, train_res=None,
-                     writer=None, best_cider=None, which='ft_xe', scheduler=None, log_and_save=True, scorer=None, scores_out=None):
+                     writer=None, best_cider=None, which='ft_xe', scheduler=None, log_and_save=True, scorer=None, scores_out=None,
+                     consensus=None):
     """Beam-search every batch (reference :165-183) and score the captions (:194-207).
     scorer: None -- no scoring, returns (token tensors per batch, seconds per batch);
             a callable `scorer(gts, gen) -> dict` on the collapsed, joined, untokenised captions;
@@ -282,22 +336,34 @@ def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='
     With `best_cider` (and log_and_save) the best checkpoint is written when CIDEr >= best_cider and the CIDEr is returned;
     a dictionary passed as `scores_out` receives the scores in either case.
     `model` may be an Ensemble (models/caption/ensemble.py); it cannot save a best checkpoint, so with one best_cider must be
-    None (or log_and_save False)."""
+    None (or log_and_save False).
+    consensus: a `Cider` with corpus statistics, or a ready reranker (DeviceCider).  With config.model.consensus_candidates = N > 1
+    every batch is decoded into N candidates per image (`decode_consensus`) and the candidate that agrees most with the others
+    under CIDEr-D is what both scorers see; with the keys off the argument changes nothing."""
     if isinstance(scorer, str) and scorer not in ('host', 'device'):
         raise ValueError("scorer must be None, a callable, 'host' or 'device', not %r" % (scorer,))
     if isinstance(scorer, str) and text_field is None:
         raise ValueError("scorer=%r needs a text_field" % (scorer,))
     if log_and_save and best_cider is not None:
         _refuse_ensemble_checkpoint(model)  # before the evaluation, not after it
+    rerank = None
+    if consensus is not None:
+        from grit_amd.config import consensus_options
+        rerank = consensus_reranker(consensus, text_field)  # (refuses a Cider without statistics before the loop)
+        if consensus_options(config)['candidates'] < 2:
+            rerank = None  # the keys are off: hypothesis 0, as without the argument
     model.eval()
     on_device = scorer == 'device'
     times, tokens, gen, gts, caption_lists = [], [], {}, {}, []
     for it, batch in enumerate(_progress(dataloader, desc=f'Epoch {epoch} - evaluation on {split}', unit='it')):
         t0 = time.time()
-        with torch.no_grad():
-            out, _ = model(batch['samples'], seq=None, use_beam_search=True, max_len=config.model.beam_len,
-                           eos_idx=config.model.eos_idx, beam_size=config.model.beam_size, out_size=1,
-                           return_probs=False, **beam_constraints(config), **beam_groups(config))
+        if rerank is not None:
+            out = decode_consensus(model, batch['samples'], config, rerank)[0][:, 0]
+        else:
+            with torch.no_grad():
+                out, _ = model(batch['samples'], seq=None, use_beam_search=True, max_len=config.model.beam_len,
+                               eos_idx=config.model.eos_idx, beam_size=config.model.beam_size, out_size=1,
+                               return_probs=False, **beam_constraints(config), **beam_groups(config))
         if out.is_cuda:
             torch.cuda.synchronize()
         times.append(time.time() - t0)

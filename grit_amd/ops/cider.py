@@ -342,3 +342,10 @@ class DeviceCider(object):
                                      ctypes.c_void_p(out64.data_ptr() if out64 is not None else 0), _lib.current_stream_ptr())
         _lib.check(st, "grit_cider_reward")
         return (out32, out64) if return_float64 else out32
+
+    def consensus(self, tokens, log_probs=None, collapse=True, return_matrix=False):
+        """Consensus reranking of the n candidates of every image under CIDEr-D (grit_amd/ops/consensus.py: device_consensus):
+        tokens [B, n, T] int64 on the device -> Consensus(tokens [B, 1, T], log_probs, score [B, n] float32, best [B], bad [B],
+        score64, sim).  It reads the word tables and the idf trie only, so no reference needs to have been cooked."""
+        from grit_amd.ops.consensus import device_consensus
+        return device_consensus(self, tokens, log_probs, collapse, return_matrix)

@@ -64,10 +64,12 @@
  *                           cider.compute_score) and datasets/caption/metrics/cider/cider_scorer.py (counts2vec, sim, compute_cider)
  *   grit_caption_scores  <- the evaluation's scores, engine/caption_engine.py:165-190 (decode, itertools.groupby, PTBTokenizer.tokenize,
  *                           compute_scores) and datasets/caption/metrics/{bleu/bleu_scorer.py, rouge/rouge.py, cider/cider_scorer.py}
+ *   grit_cider_consensus <- nothing in the reference: consensus (minimum-Bayes-risk) reranking of the candidates of an image under
+ *                           CIDEr-D, built from the same steps as grit_cider_reward; the host form is grit_amd/ops/consensus.py
  *   grit_jpeg_probe, grit_jpeg_entropy, grit_jpeg_reconstruct
  *                        <- PIL's Image.open(path).convert('RGB') in the dataset workers (datasets/caption/field.py:65,
  *                           tools/extract_features.py:42): libjpeg-turbo's baseline decode at its defaults
- * (none of the last sixteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ * (none of the last seventeen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
  *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
@@ -79,7 +81,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 56
+#define GRIT_ABI_VERSION 57
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -1013,6 +1015,37 @@ typedef struct {
 } grit_cider_tables;
 int grit_cider_reward(const int64_t* tokens, int rows, int T, const int32_t* slots, int beam, const grit_cider_tables* tab,
                       float* out32, double* out64, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Consensus (minimum-Bayes-risk) reranking of the n candidate captions of an image under CIDEr-D (Devlin et al. 2015, "consensus
+ * reranking"): the candidate that agrees most with the others is chosen.  The references of a candidate are the OTHER candidates of
+ * its image, not ground-truth captions; a candidate as a reference has the vector it has as a hypothesis (tf * idf at each n-gram's
+ * first occurrence, norms summed in first-occurrence order, length in bigram occurrences), so nothing is cooked on the host.
+ * The host form, and the yardstick of the tests, is grit_amd/ops/consensus.py: consensus_host.
+ *
+ * tokens [images, n, T] int64, contiguous.  A row's caption is its words in front of the first <eos>, with collapse != 0 after
+ * dropping every word equal to its predecessor, tokenised through the per-word tables exactly as grit_cider_reward and
+ * grit_caption_scores do.  With v_i the tf-idf vectors of candidate i:
+ *     sim[b, i, j]  = the clipped similarity of hypothesis v_i against reference v_j (min(w_h, w_r) * w_r per shared n-gram, over the
+ *                     norms, Gaussian length penalty, mean over the orders) for i != j, 0 for i == j: NOT symmetric;
+ *     score[b, i]   = (sum over j != i, j ascending, of sim[b, i, j]) / (n - 1) * 10, 0 when n == 1;
+ *     best[b]       = the smallest i whose score is maximal.
+ * sim64 [images, n, n] float64 or NULL; score64 [images, n] float64; score32 [images, n] float32 or NULL; best [images] int32;
+ * bad [images] int32.  An empty caption has similarity 0 in both directions and is still a candidate.  If any row of an image holds
+ * a word id outside [0, vocab) in front of its first <eos> (the host form raises), every sim and score of that image is NaN,
+ * best = 0 and bad = 1; bad = 0 otherwise.  Other images are unaffected.
+ *
+ * Two launches (cook every row; score and select per image), float64 arithmetic with every sum in the host's order, no atomics, no
+ * synchronisation, no allocation: two calls on the same input are bit-identical.  workspace: grit_cider_consensus_workspace(images,
+ * n, T) bytes of device memory, no initialisation needed (0 for arguments that the call itself refuses).
+ * Of `tab` only expansion, word_meta, vocab, width, the idf trie, sigma and log_corpus are read: tables without any reference slot
+ * (n_slots == 0) are accepted.  Limits: n > GRIT_CONSENSUS_MAX_CANDIDATES, width > GRIT_CIDER_MAX_EXPANSION or
+ * T * width > GRIT_CIDER_MAX_TOKENS: GRIT_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_CONSENSUS_MAX_CANDIDATES 32
+long grit_cider_consensus_workspace(int images, int n, int T);
+int grit_cider_consensus(const int64_t* tokens, int images, int n, int T, int collapse, const grit_cider_tables* tab, double* sim64,
+                         double* score64, float* score32, int32_t* best, int32_t* bad, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * The evaluation's caption scores (reference engine/caption_engine.py:165-190: decode the best beam up to <eos>, collapse repeated

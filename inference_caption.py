@@ -2,7 +2,7 @@
 (`state_dict` key, strict=False), NestedTensor batch of one, beam search, token ids -> words through vocab.json.
 
     python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth [ckpt2.pth ...]] [--vocab data/vocab.json] [--beam 5]
-                                [--groups G --diversity X] [--n-best N]
+                                [--groups G --diversity X] [--n-best N] [--sample N] [--consensus --consensus-corpus captions.json]
 
 Several checkpoints: one model per checkpoint, captioned together by models.caption.ensemble.Ensemble (their word
 log-probabilities averaged at every beam step).
@@ -187,11 +187,49 @@ def build_parser():
     ap.add_argument('--top-k', type=int, default=0, help="sample among the k most probable words only (0: all)")
     ap.add_argument('--top-p', type=float, default=1.0, help="sample inside the smallest nucleus of this mass")
     ap.add_argument('--seed', type=int, default=None, help="sampling seed (default: torch's device generator)")
+    ap.add_argument('--consensus', action='store_true',
+                    help="rerank what --n-best N or --sample N produced by consensus under CIDEr-D: the chosen caption first, then "
+                         "the candidates with their consensus scores (needs --consensus-corpus)")
+    ap.add_argument('--consensus-corpus', default=None, metavar='FILE',
+                    help="JSON list of caption lists, one list per image: the corpus of the CIDEr-D document frequencies")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.consensus and not a.consensus_corpus:
+        ap.error("--consensus needs --consensus-corpus FILE (the captions the CIDEr-D document frequencies come from)")
+    if a.consensus and max(a.n_best, a.sample) < 2:
+        ap.error("--consensus reranks several candidates: give --n-best N or --sample N with N > 1")
+    return a
+
+
+def consensus_cider(corpus_path):
+    """The `Cider` of --consensus-corpus: a JSON list of caption lists, one per image, tokenised by the native tokenizer."""
+    from grit_amd.datasets.caption.metrics import Cider, PTBTokenizer
+    with open(corpus_path) as f:
+        corpus = json.load(f)
+    if not isinstance(corpus, list) or not corpus or not all(isinstance(c, list) and c and all(isinstance(s, str) for s in c) for c in corpus):
+        raise ValueError("%s: expected a JSON list of non-empty lists of captions, one list per image" % corpus_path)
+    return Cider(PTBTokenizer.tokenize({i: caps for i, caps in enumerate(corpus)}))
+
+
+def print_consensus(tokens, cider, vocab_path, eos_idx=3):
+    """tokens [n, T] on the device: the candidates of one image.  Prints the caption chosen by consensus, then every candidate
+    with its consensus score."""
+    from grit_amd.ops.cider import DeviceCider
+    with open(vocab_path) as f:
+        vocab = json.load(f)
+    itos = vocab['itos'] if isinstance(vocab, dict) and 'itos' in vocab else vocab
+    chosen = DeviceCider(cider, itos, eos_token=itos[eos_idx], device=tokens.device).consensus(tokens.unsqueeze(0))
+    print(decode(chosen.tokens[0], vocab_path, eos_idx)[0])
+    for score, line in zip(chosen.score[0].tolist(), decode(tokens, vocab_path, eos_idx)):
+        print('%8.4f  %s' % (score, line))
+
+
 def run_main():
-    a = build_parser().parse_args()
+    a = parse_args()
     config = default_config(**{'model.beam_min_len': a.min_len, 'model.beam_no_repeat_ngram': a.no_repeat_ngram,
                                'model.beam_no_repeat_word': a.no_repeat_word, 'model.beam_suppress': list(a.suppress),
                                'model.beam_length_penalty': a.length_penalty, 'model.beam_groups': a.groups,
@@ -207,6 +245,14 @@ def run_main():
         rgb = np.asarray(Image.open(a.img).convert('RGB'), dtype=np.float32) / 255.0
         mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
         image = torch.from_numpy(((rgb - mean) / std).transpose(2, 0, 1))
+    if a.consensus:  # (the vocabulary is needed: consensus compares words, not ids)
+        cider = consensus_cider(a.consensus_corpus)
+        if a.sample > 0:
+            tokens, _ = sample_tokens(model, image, config, a.sample, a.temperature, a.top_k, a.top_p, a.seed)
+        else:
+            tokens = caption_tokens(model, image, config, a.beam, a.n_best)[0][0]
+        print_consensus(tokens, cider, a.vocab, config.model.eos_idx)
+        return
     if a.sample > 0:
         tokens, _ = sample_tokens(model, image, config, a.sample, a.temperature, a.top_k, a.top_p, a.seed)
         for line in (decode(tokens, a.vocab, config.model.eos_idx) if os.path.exists(a.vocab) else tokens.tolist()):

@@ -26,7 +26,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from grit_amd.config import default_config, load_yaml
+from grit_amd.config import consensus_options, default_config, load_yaml
 from grit_amd.data import SyntheticLoader
 from grit_amd.amp import Bf16Compute
 from grit_amd.ddp import BucketedDataParallel
@@ -125,6 +125,10 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
         raise ValueError("exp.eval_scorer must be 'host' or 'device', not %r" % (eval_scorer,))
     if evaluates and eval_scorer == 'device' and not use_cuda:  # said before the first epoch, not after it
         raise ValueError("exp.eval_scorer='device' scores the captions in a HIP kernel and there is no GPU: set exp.eval_scorer='host'")
+    # model.consensus_candidates > 1: the evaluation reranks that many candidates per image by consensus under `cider`
+    consensus = cider if consensus_options(config)['candidates'] > 1 else None
+    if evaluates and consensus_options(config)['candidates'] > 1 and cider is None:
+        raise ValueError("model.consensus_candidates > 1 needs the training corpus' Cider (main(..., cider=Cider(gts)))")
     # carried across epochs and, through every epoch's checkpoint, across a resume (reference best_cider_val / best_cider_test)
     best_cider = {'valid': 0.0, 'test': 0.0}
     if resumed_best is not None and len(resumed_best) == 2:
@@ -161,7 +165,7 @@ def main(gpu, config, dataloaders=None, text_field=None, cider=None, tokenizer_p
             scores = {}
             evaluate_metrics(model, optimizers, dataloaders[split + '_dict'], text_field, epoch=epoch, split=split, config=config,
                              train_res=res, best_cider=best_cider[split], which=phase, scheduler=scheduler, log_and_save=save,
-                             scorer=eval_scorer, scores_out=scores)
+                             scorer=eval_scorer, scores_out=scores, consensus=consensus)
             best_cider[split] = max(best_cider[split], scores['CIDEr'])
             res[split + '_scores'], res['best_cider_' + split] = scores, best_cider[split]
         results.append(res)
