@@ -123,7 +123,7 @@ _DETECTION_DEFAULTS = {
     'exp': dict(seed=42, save_dir='', rank=0, ngpus_per_node=8, world_size=64, checkpoint='', eval=False, resume=False,
                 eval_every_iters=-1),
     'model': dict(
-        has_attr_head=False,
+        has_attr_head=False, num_attr_classes=400,
         backbone=dict(backbone_name='swin_base_win7_384_22k', pre_trained='imagenet'),
         det_module=dict(reduced_dim=512, dim_feedforward=1024, num_heads=8, num_layers=6, num_levels=4, num_points=4,
                         return_intermediate=True, num_queries=150, num_classes=1849, dropout=0.1, activation='relu',

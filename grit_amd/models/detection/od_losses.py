@@ -5,12 +5,17 @@ The criterion of a step is two launches forward for ALL output layers together -
 and one launch backward; the host is never waited for.  The reference does, per output layer, a dozen elementwise ops for the cost,
 a copy to the host, one scipy solve per image, a one-hot target and some fifteen elementwise ops for the focal loss.
 
-Out of scope, each refused: the `masks` loss, `enc_outputs`, attribute heads (`attr_logits` / weighted_attr_loss).
+With an attribute head (`attr_logits` in the outputs) the reference's weighted_attr_loss of the last layer joins as 'loss_attr':
+one more launch each way (grit_amd/ops/det_attr.py), fed by the last layer's slab of the same match -- no second match, and no
+host-side index lists or `if target['has_attr']` on a device scalar as in the reference.
+
+Out of scope, each refused: the `masks` loss, `enc_outputs`.
 """
 import torch
 from torch import nn
 import torch.nn.functional as F
 
+from grit_amd.ops import det_attr as _det_attr
 from grit_amd.ops import det_eval as _det_eval
 from grit_amd.ops import det_loss as _det
 
@@ -75,7 +80,8 @@ class SetCriterion(nn.Module):
     GIoU) -- for the last output layer and every auxiliary one in the same launches.
 
     forward(outputs, targets) -> {'loss_ce', 'class_error', 'loss_bbox', 'loss_giou', 'cardinality_error'} and the same keys
-    without class_error suffixed `_i` for outputs['aux_outputs'][i]; 0-d fp32 device tensors.
+    without class_error suffixed `_i` for outputs['aux_outputs'][i]; 0-d fp32 device tensors.  With outputs['attr_logits'] [B, Q, A]
+    also 'loss_attr' (last layer only); the targets may then carry 'attributes' [T, A] and 'has_attr'.
 
     `losses` is kept for the reference's signature and only checked for 'masks': like the reference's forward, every call computes
     labels, boxes and cardinality whatever the list says.  When the outputs carry 'pred_logits_all' / 'pred_boxes_all' (the
@@ -93,8 +99,6 @@ class SetCriterion(nn.Module):
             raise TypeError("SetCriterion: targets must be a list with one dict per image, got %s" % type(targets).__name__)
         if 'enc_outputs' in outputs:
             raise NotImplementedError("SetCriterion: enc_outputs (two-stage proposals) are not implemented")
-        if 'attr_logits' in outputs:
-            raise NotImplementedError("SetCriterion: the attribute head's loss is not implemented")
         if len(targets) == 0:
             return {}
         layers = list(outputs.get('aux_outputs', ())) + [outputs]
@@ -105,7 +109,8 @@ class SetCriterion(nn.Module):
         else:
             logits = torch.stack([o['pred_logits'] for o in layers]).float()
             boxes = torch.stack([o['pred_boxes'] for o in layers]).float()
-        packed = _det.pack_targets(targets)
+        attr_logits = outputs.get('attr_logits')
+        packed = _det.pack_targets(targets, num_attr=None if attr_logits is None else attr_logits.shape[-1])
         _, match_t = self.matcher.match_layers(logits, boxes, packed)
         out = _det.set_criterion(logits, boxes, match_t, packed, self.focal_alpha)
         names = (('loss_ce', _det.LOSS_CE), ('loss_bbox', _det.LOSS_BBOX), ('loss_giou', _det.LOSS_GIOU),
@@ -119,6 +124,8 @@ class SetCriterion(nn.Module):
         for i in range(last):
             for name, col in names:
                 losses['%s_%d' % (name, i)] = at(i, col)
+        if attr_logits is not None:  # the last layer only, as the reference; its slab of match_t is a contiguous view
+            losses['loss_attr'] = _det_attr.attr_loss(attr_logits.float(), match_t[last], packed)
         for key in list(losses):
             if key.startswith('cardinality_error'):
                 losses[key] = losses[key].detach()

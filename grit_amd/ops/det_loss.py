@@ -19,22 +19,64 @@ _p = _lib.ptr
 
 class PackedTargets(object):
     """labels [sum T + 1] int64, boxes [sum T + 1, 4] fp32 (one padding row, so that an empty batch is no null pointer),
-    offsets [B + 1] int32 and num_boxes [1] fp32 on the device; counts and t_max on the host."""
+    offsets [B + 1] int32 and num_boxes [1] fp32 on the device; counts and t_max on the host.  For the attribute head
+    (grit_amd/ops/det_attr.py) also attributes [sum T + 1, A] uint8, rows aligned with labels, and has_attr [B] bool on the
+    device.  Both are None when no target carried 'attributes' or 'has_attr' and the caller named no number of attribute classes:
+    a batch without attributes is packed with exactly the copies it always was."""
 
-    def __init__(self, labels, boxes, offsets, num_boxes, counts):
+    def __init__(self, labels, boxes, offsets, num_boxes, counts, attributes=None, has_attr=None):
         self.labels, self.boxes, self.offsets, self.num_boxes = labels, boxes, offsets, num_boxes
         self.counts = list(counts)
         self.t_max = max(self.counts) if self.counts else 0
+        self.attributes, self.has_attr = attributes, has_attr
+
+    def add_attributes(self, num_attr):
+        """Zero attribute rows and has_attr = False where the targets carried none."""
+        if self.attributes is None:
+            self.attributes = torch.zeros((self.labels.shape[0], int(num_attr)), dtype=torch.uint8, device=self.labels.device)
+        if self.has_attr is None:
+            self.has_attr = torch.zeros(len(self.counts), dtype=torch.bool, device=self.labels.device)
 
     def __len__(self):
         return len(self.counts)
 
 
-def pack_targets(targets, device=None):
-    """targets: a list (one per image) of {'labels': [T_i] int, 'boxes': [T_i, 4] cxcywh normalised} device tensors."""
+def _pack_attributes(targets, counts, device, num_attr):
+    """(attributes [sum T + 1, A] uint8 or None, has_attr [B] bool), both on the device.  An image without 'attributes' gets zero
+    rows, one without 'has_attr' is False.  has_attr may be a Python bool, a CPU tensor or a device tensor: device values are
+    stacked where they are, host values travel through pinned memory -- nothing is read back."""
+    given = [t.get('attributes') for t in targets]
+    for a, n in zip(given, counts):
+        if a is None:
+            continue
+        if a.dim() != 2 or a.shape[0] != n:
+            raise _lib.GritHipError("pack_targets: attributes %s for %d labels" % (tuple(a.shape), n))
+        if num_attr is None:
+            num_attr = int(a.shape[1])
+        elif int(a.shape[1]) != int(num_attr):
+            raise _lib.GritHipError("pack_targets: %d attribute classes in the targets, %d expected" % (a.shape[1], num_attr))
+    attributes = None
+    if num_attr is not None:
+        rows = [(a != 0).to(torch.uint8) if a is not None else torch.zeros((n, num_attr), dtype=torch.uint8, device=device)
+                for a, n in zip(given, counts)]
+        attributes = torch.cat(rows + [torch.zeros((1, num_attr), dtype=torch.uint8, device=device)])
+    flags = [t.get('has_attr', False) for t in targets]
+    on_device = [isinstance(f, torch.Tensor) and f.is_cuda for f in flags]
+    host = torch.tensor([False if dev else bool(f) for f, dev in zip(flags, on_device)], dtype=torch.bool)
+    has_attr = host.pin_memory().to(device, non_blocking=True) if device.type == 'cuda' else host.to(device)
+    if any(on_device):
+        has_attr = torch.stack([f.reshape(()).to(device=device, dtype=torch.bool) if dev else has_attr[i]
+                                for i, (f, dev) in enumerate(zip(flags, on_device))])
+    return attributes, has_attr
+
+
+def pack_targets(targets, device=None, num_attr=None):
+    """targets: a list (one per image) of {'labels': [T_i] int, 'boxes': [T_i, 4] cxcywh normalised} device tensors, optionally
+    with 'attributes' [T_i, A] (multi-hot, any dtype) and 'has_attr' (bool, CPU or device tensor).  num_attr: the number of
+    attribute classes the caller expects; with it the attribute rows exist even when no target carries any."""
     if len(targets) == 0:
         raise _lib.GritHipError("pack_targets: an empty batch has nothing to pack")
-    _lib.require_device(*[t[k] for t in targets for k in ('labels', 'boxes')])
+    _lib.require_device(*[t[k] for t in targets for k in ('labels', 'boxes')] + [t.get('attributes') for t in targets])
     device = targets[0]['boxes'].device if device is None else torch.device(device)
     counts = [int(t['labels'].shape[0]) for t in targets]
     for t, n in zip(targets, counts):
@@ -54,7 +96,10 @@ def pack_targets(targets, device=None):
         num_boxes = torch.clamp(num_boxes / get_world_size(), min=1)
     else:
         num_boxes = torch.tensor([max(float(offs[-1]), 1.0)], dtype=torch.float32).pin_memory().to(device, non_blocking=True)
-    return PackedTargets(labels, boxes, offsets, num_boxes, counts)
+    attributes = has_attr = None
+    if num_attr is not None or any('attributes' in t or 'has_attr' in t for t in targets):
+        attributes, has_attr = _pack_attributes(targets, counts, device, num_attr)
+    return PackedTargets(labels, boxes, offsets, num_boxes, counts, attributes, has_attr)
 
 
 def _check_outputs(logits, boxes, packed, what):

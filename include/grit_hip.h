@@ -81,7 +81,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 57
+#define GRIT_ABI_VERSION 58
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -1136,6 +1136,45 @@ int grit_det_loss_fwd_f32(const float* logits, const float* boxes, const int64_t
 int grit_det_loss_bwd_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
                           const int32_t* tgt_offsets, const int32_t* match_t, int L, int B, int Q, int K, float alpha,
                           const float* num_boxes, const float* coef, int ldc, float* dlogits, float* dboxes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Detector attribute head (reference models/detection/heads.py AttrHead :33-51, od_losses.py weighted_attr_loss :141-177).
+ *
+ * grit_attr_embed_cat: the head's front in one launch, one wave per row.  obj_h [rows, d], embed [K, d] and out [rows, 2 d] share
+ * one dtype (bf16 != 0: bf16, else fp32); logits [rows, K] are fp32, or bf16 with logits_bf16 != 0 (widened to fp32 first).
+ *     labels[r] int32 = the FIRST index of the maximum of 1 / (1 + expf(-logit)) evaluated in fp32 -- the reference's
+ *                       argmax(sigmoid(.)), which saturates at 1.0f from a logit of about 16.7: NOT the argmax of the logits
+ *     out[r] = [ obj_h[r] | embed[labels[r]] ], copied bit for bit (16 bytes per lane where d * element size and the three base
+ *              addresses are multiples of 16, else element by element)
+ * NaN logits are outside the contract (the label is then some index in [0, K)).  BOUND: rows * K, rows * 2 d and K * d < 9e15.
+ *
+ * grit_attr_embed_grad: dweight [K, d] = for every class the sum, in row order, of dcat[r, col0 .. col0 + d) over the rows with
+ * labels[r] == k; dcat [rows, ld] (col0 + d <= ld) and dweight share one dtype (bf16 flag as above), the sum is fp32.  One wave
+ * per (class, 64 columns); no atomics, two calls give identical bytes; a class nobody chose gets zeros, a label outside [0, K)
+ * contributes nowhere.  BOUND: d <= 65535 * 64 (above it GRIT_ERR_UNSUPPORTED), rows * ld and K * d < 9e15.
+ *
+ * grit_det_attr_fwd_f32: attr_logits [B, Q, A] fp32, attributes [sum T + 1, A] uint8 (0 / 1, rows aligned with tgt_labels),
+ * tgt_offsets [B + 1] int32, has_attr [B] uint8, match_t [B, Q] int32 (the LAST layer's slab of grit_det_match_f32).  Over the rows
+ * (b, q) with has_attr[b] != 0 and 0 <= t = match_t[b, q] < T_b, x = attr_logits[b, q], y = attributes[offset_b + t]:
+ *     bce = max(x, 0) - x y + log1p(exp(-|x|))                                    (fp32 per element, sums in float64)
+ *     loss[0] = sum(bce y) / N1 + sum(bce (1 - y)) / N0,  N1 = sum(y), N0 = sum(1 - y) (integers); a term with a zero count is 0
+ * totals [2] int64 = (N1, N0), which the backward reads.  partials [B * chunks, 2] float64 and counts [B * chunks, 2] int64 are
+ * workspace, chunks = ceil(Q / GRIT_DET_LOSS_ROWS); ticket as for grit_det_loss_fwd_f32.  The counts are this rank's.
+ *
+ * grit_det_attr_bwd_f32: one launch; writes EVERY element of dlogits [B, Q, A]:
+ *     (sigmoid(x) - y) (y / N1 + (1 - y) / N0) upstream[0] on the rows above, 0 elsewhere; upstream: ONE float in device memory.
+ * BOUND (both): B * Q * A < 9e15 and B * chunks < 2^31, else GRIT_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------------------------------------ */
+int grit_attr_embed_cat(const void* obj_h, const void* logits, const void* embed, void* out, int32_t* labels, int rows, int K, int d,
+                        int bf16, int logits_bf16, void* stream);
+int grit_attr_embed_grad(const void* dcat, const int32_t* labels, void* dweight, int rows, int K, int d, int ld, int col0, int bf16,
+                         void* stream);
+int grit_det_attr_fwd_f32(const float* attr_logits, const uint8_t* attributes, const int32_t* tgt_offsets, const uint8_t* has_attr,
+                          const int32_t* match_t, int B, int Q, int A, double* partials, int64_t* counts, unsigned int* ticket,
+                          float* loss, int64_t* totals, void* stream);
+int grit_det_attr_bwd_f32(const float* attr_logits, const uint8_t* attributes, const int32_t* tgt_offsets, const uint8_t* has_attr,
+                          const int32_t* match_t, int B, int Q, int A, const int64_t* totals, const float* upstream, float* dlogits,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Detector evaluation (reference models/detection/od_losses.py PostProcess :326-356; datasets/detection/metrics/cocoeval.py

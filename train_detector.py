@@ -1,6 +1,6 @@
 """Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
 
-    python train_detector.py --synthetic [--augment] --steps 3 [--batch-size 2] [--size 224] [--bf16] [--eval] [key=value ...]
+    python train_detector.py --synthetic [--augment] [--attr] --steps 3 [--batch-size 2] [--size 224] [--bf16] [--eval] [key=value ...]
 
 The Visual Genome / LMDB readers and the hook-based solver are out of scope of this build, so the only data source here is
 `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
@@ -10,6 +10,9 @@ through datasets.detection.make_transforms('train', 'train') -- flip, random res
 collate_detection, which resamples the batch on the device (`--size` does not apply: the recipe decides the sizes).
 `--bf16` trains on the path the captioner uses (grit_amd.amp.Bf16Compute: bf16 compute copies, fp32 masters, flat AdamW and gradient
 clipping on the device, the reference's four parameter groups and MultiStepLR; engine.det_engine.build_optimizers_schedulers).
+`--attr` trains the attribute head as well (model.has_attr_head, models/detection/heads.py): every other image carries seeded
+multi-hot attributes, attr_loss_coef is 1, the head has its own AdamW (optimizer.sp_names=['attr_head']) and `loss_attr` is printed
+with the other losses.
 `--eval` evaluates after the steps (engine.det_engine.evaluate: PostProcess and the COCO-style box evaluation on the device,
 datasets.detection.metrics.CocoEvaluator) on `--eval-batches` seeded synthetic batches and prints the losses and the box mAP table.
 Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
@@ -37,6 +40,17 @@ def synthetic_batch(generator, batch_size, size, num_classes, max_targets, devic
         targets.append({'labels': torch.randint(0, num_classes, (n,), generator=generator).to(device),
                         'boxes': torch.cat([centre, wh], 1).to(device)})
     return NestedTensor(images.to(device), mask.to(device), any_padding=False), targets
+
+
+def add_synthetic_attributes(generator, targets, num_attr, device):
+    """--attr: every other image of the batch gets has_attr=True and a multi-hot 'attributes' [T, num_attr] uint8 with about 2 % ones
+    (Visual Genome annotates a few attributes per object); the others has_attr=False and no attributes."""
+    for i, t in enumerate(targets):
+        t['has_attr'] = i % 2 == 0
+        if t['has_attr']:
+            n = int(t['labels'].shape[0])
+            t['attributes'] = (torch.rand(n, num_attr, generator=generator) < 0.02).to(torch.uint8).to(device)
+    return targets
 
 
 def synthetic_split(generator, batches, batch_size, size, num_classes, max_targets, device):
@@ -91,6 +105,9 @@ def main():
     ap.add_argument('--size', type=int, default=224, help='image side')
     ap.add_argument('--max-targets', type=int, default=30)
     ap.add_argument('--bf16', action='store_true', help='bf16 compute + fp32 masters: flat AdamW and device gradient clipping')
+    ap.add_argument('--attr', action='store_true',
+                    help='with the attribute head (model.has_attr_head): synthetic attributes on every other image, attr_loss_coef 1, '
+                         "and the reference's second optimizer for the head (optimizer.sp_names=['attr_head'])")
     ap.add_argument('--steps-per-epoch', type=int, default=0,
                     help='with --bf16: step the lr schedulers once per this many steps (0: never within a run)')
     ap.add_argument('--eval', action='store_true', help='after the steps: losses and COCO-style box mAP on seeded synthetic batches')
@@ -100,6 +117,8 @@ def main():
     if not args.synthetic:
         ap.error("only --synthetic is available: the Visual Genome readers are not part of this build")
     over = {'model.backbone.pre_trained': 'none'}
+    if args.attr:
+        over.update({'model.has_attr_head': True, 'model.det_module.loss.attr_loss_coef': 1.0, 'optimizer.sp_names': ['attr_head']})
     for item in args.overrides:
         key, _, value = item.partition('=')
         try:
@@ -120,6 +139,8 @@ def main():
         from grit_amd.amp import Bf16Compute
         model = Bf16Compute(model)
         optimizer, schedulers = build_optimizers_schedulers(model, config)
+    elif args.attr:  # the recipe's grouping: the head's own AdamW at sp_lr beside the main one
+        optimizer, schedulers = build_optimizers_schedulers(model, config)
     else:
         optimizer = _plain_optimizer(model, config)
     g = torch.Generator().manual_seed(config.exp.seed)
@@ -133,6 +154,8 @@ def main():
             samples, targets = augmented_batch(g, batch_size, config.model.det_module.num_classes, args.max_targets, device, transform)
         else:
             samples, targets = synthetic_batch(g, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
+        if args.attr:
+            add_synthetic_attributes(g, targets, config.model.num_attr_classes, device)
         total, losses = train_step(model, criterion, optimizer, samples, targets, config.optimizer.clip_max_norm)
         print('step %d  loss %.5f  %s' % (step, float(total), {k: round(float(v), 5) for k, v in sorted(losses.items())}))
         if args.steps_per_epoch > 0 and (step + 1) % args.steps_per_epoch == 0:
