@@ -47,6 +47,9 @@ _DEFAULTS = {
         # diverse beam search of evaluation and inference: beam_groups groups of beam_size / beam_groups beams searched in turn, a
         # group paying beam_diversity per earlier choice of the same word at a step (1 group: the plain search, as in the reference)
         beam_groups=1, beam_diversity=0.0,
+        # forced words of inference: every entry is one set, "dog|dogs" a set of two alternatives; the caption must hold a word of
+        # every set (constrained beam search by dynamic beam allocation, grit_amd/ops/beam.py).  Empty: off
+        beam_force_words=(),
         # consensus (minimum-Bayes-risk) reranking of evaluation under CIDEr-D (grit_amd/ops/consensus.py): of consensus_candidates
         # candidates per image the one that agrees most with the others is scored (0 or 1: off, hypothesis 0 as in the reference).
         # consensus_decode 'beam': the N best final hypotheses of the search configured above (N <= beam_size); 'sample': N samples
@@ -85,6 +88,31 @@ def beam_groups(config):
     written before they existed gives the defaults (one group: the plain search)."""
     m = config.model
     return dict(num_groups=getattr(m, 'beam_groups', 1), diversity=getattr(m, 'beam_diversity', 0.0))
+
+
+def force_words_ids(specs, stoi, batch_size=1):
+    """The sets of forced words that `specs` names ("dog|dogs", "frisbee": one set per entry, alternatives separated by |) as the
+    force_words tensor of Transformer.forward / Ensemble.forward, int64 [batch_size, sets, words] padded with -1 and the same for
+    every image, or None without specs.  `stoi` maps a word to its id (a dict, or the list of words in id order); a word that the
+    vocabulary does not hold is a ValueError that names it."""
+    import torch
+    specs = [specs] if isinstance(specs, str) else list(specs or ())
+    if not specs:
+        return None
+    if not isinstance(stoi, dict):
+        stoi = {word: i for i, word in enumerate(stoi)}
+    sets = []
+    for spec in specs:
+        words = [w.strip() for w in str(spec).split('|') if w.strip()]
+        if not words:
+            raise ValueError("forced words: %r names no word" % (spec,))
+        for w in words:
+            if w not in stoi:
+                raise ValueError("forced word %r is not in the vocabulary" % w)
+        sets.append([int(stoi[w]) for w in words])
+    width = max(len(ids) for ids in sets)
+    table = torch.tensor([ids + [-1] * (width - len(ids)) for ids in sets], dtype=torch.int64)
+    return table.unsqueeze(0).repeat(batch_size, 1, 1)
 
 
 def consensus_options(config):

@@ -116,7 +116,7 @@ constexpr int kMaxMaps = 8;
 struct MapTable { const float* p[kMaxMaps]; };  // by value in the kernel arguments: nothing to upload, nothing to keep alive
 
 struct OneMap {
-    static constexpr bool kBans = false;
+    static constexpr bool kBans = false, kForced = false;
     const float* p;
     __device__ __forceinline__ float at(size_t i) const { return p[i]; }
     __device__ __forceinline__ bool aligned16(size_t i) const { return (((uintptr_t)(p + i)) & 15) == 0; }
@@ -124,7 +124,7 @@ struct OneMap {
 };
 
 struct MeanMaps {
-    static constexpr bool kBans = false;
+    static constexpr bool kBans = false, kForced = false;
     MapTable t;
     int n;
     float factor;
@@ -177,6 +177,33 @@ struct Banned : Base {
     static constexpr bool kBans = true;
     Bans bans;
 };
+
+// The step with forced words (grit_beam_step_forced_f32): the constrained source plus the sets of forced words per image and the
+// mask of met sets per beam row.  Stage 1 reads them for one more ban: <eos> while a row has not met every set.
+constexpr int kMaxSets = GRIT_BEAM_MAX_FORCED_SETS, kMaxWords = GRIT_BEAM_MAX_FORCED_WORDS;
+struct ForcedSets {
+    const int64_t* words;  // [B, C, W], -1 = padding
+    const int* met;        // [rows] or NULL: every row starts from the image's empty sets
+    int C, W;
+};
+
+template <class Base>
+struct Forced : Banned<Base> {
+    static constexpr bool kForced = true;
+    ForcedSets forced;
+};
+
+__device__ __forceinline__ int met_of_row(const ForcedSets& f, int b, int row_id) {
+    if (f.met) return f.met[row_id];
+    const int64_t* words = f.words + (size_t)b * f.C * f.W;
+    int met = 0;
+    for (int c = 0; c < f.C; ++c) {
+        bool any = false;
+        for (int q = 0; q < f.W; ++q) any = any || words[c * f.W + q] >= 0;
+        if (!any) met |= 1 << c;
+    }
+    return met;
+}
 
 // The banned words of one live beam row as a bitmap over the workgroup's vocabulary slice [v0, v1): a thread per history
 // position finds the n-gram continuations, further threads add the fixed rules.  The caller synchronises afterwards.
@@ -238,6 +265,10 @@ void beam_partial(Src logp, long ld, const float* __restrict__ seq_lp, const flo
         __shared__ unsigned bits[kMaxSlice / 32];
         if (alive && v0 < v1) {  // uniform over the workgroup
             mark_bans(logp.bans, row_id, v0, v1, hist, bits);
+            if constexpr (Src::kForced) {  // a row that still owes a forced word may not end
+                if (tid == 130 && eos >= v0 && eos < v1 && met_of_row(logp.forced, b, row_id) != (1 << logp.forced.C) - 1)
+                    atomicOr(&bits[(eos - v0) >> 5], 1u << ((eos - v0) & 31));  // LDS
+            }
             __syncthreads();
             auto score = [&](float x, unsigned banned) { return banned ? -INFINITY : base + x; };
             if (logp.aligned16(row + v0)) {
@@ -416,6 +447,154 @@ void beam_merge_groups(Src logp, long ld, const float* __restrict__ seq_lp, cons
     }
 }
 
+// Stage 2 of the step with forced words (grit_beam_step_forced_f32): one workgroup per image, every candidate of the image in LDS.
+// Row j owns the slots [j * per, (j + 1) * per), per = k + C * W: first its k best candidates out of stage 1's lists (a finished
+// row: its word-0 candidate alone), then one slot per forced word.  A thread per history position finds the n-gram continuations
+// of a row as mark_bans does; a thread per slot then tests its forced word against them and the fixed rules, drops the word when an
+// earlier slot of the row holds it already, and banks the candidate.  The round-robin over the banks is a sort by (rank inside
+// the bank, bank descending): both are counted, a thread per candidate, and the k first store the outputs at their position.  The
+// counting loops compare one integer per candidate (the order of `better` as a 64-bit key; rank and bank as one int), so that
+// their LDS reads do not wait for one another.
+constexpr int kMaxForcedCand = kMaxK * (kMaxK + kMaxSets * kMaxWords);  // 320
+
+template <class Src>
+__global__ __launch_bounds__(kBeamThreads)
+void beam_forced_select(Src logp, long ld, Bans bans, ForcedSets f, const float* __restrict__ seq_lp,
+                        const float* __restrict__ seq_mask, const int64_t* __restrict__ prev_words, int eos, int first_step, int cur,
+                        int V, int k, int parts, const float* __restrict__ ws_val, const int* __restrict__ ws_idx,
+                        int64_t* __restrict__ sel_beam, int64_t* __restrict__ sel_word, float* __restrict__ new_lp,
+                        float* __restrict__ new_mask, float* __restrict__ picked, int* __restrict__ new_met) {
+    constexpr int kNone = 0x7fffffff, kInvalid = -2;
+    __shared__ float c_score[kMaxForcedCand];
+    __shared__ int c_key[kMaxForcedCand], c_met[kMaxForcedCand], c_bank[kMaxForcedCand], c_slot[kMaxForcedCand];
+    __shared__ uint64_t c_ord[kMaxForcedCand];
+    __shared__ unsigned char c_valid[kMaxForcedCand];
+    __shared__ int64_t s_fw[kMaxSets * kMaxWords];
+    __shared__ int64_t s_hist[kMaxK][kMaxHistory], s_next[kMaxK][kMaxHistory];
+    __shared__ float s_alive[kMaxK], s_base[kMaxK];
+    __shared__ int s_met[kMaxK];
+    __shared__ float w_val[128];
+    __shared__ int w_idx[128];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int CW = f.C * f.W, per = k + CW, N = cur * per, full = (1 << f.C) - 1;
+    const int t = bans.t, n = bans.ngram, lists = parts * k, n_ws = cur * lists;  // n_ws <= 128
+
+    if (tid < CW) s_fw[tid] = f.words[(size_t)b * CW + tid];
+    if (tid >= 64 && tid < 64 + cur) {
+        const int j = tid - 64, row_id = b * cur + j;
+        s_alive[j] = first_step ? 1.f : seq_mask[row_id] * (prev_words[row_id] != (int64_t)eos ? 1.f : 0.f);
+        s_base[j] = seq_lp[row_id];
+        s_met[j] = met_of_row(f, b, row_id);
+    }
+    for (int e = tid; e < n_ws; e += kBeamThreads) {  // entry r of list l of row j
+        const int l = e / k, r = e - l * k;
+        w_val[e] = ws_val[((size_t)b * cur * parts + l) * kMaxK + r];
+        w_idx[e] = ws_idx[((size_t)b * cur * parts + l) * kMaxK + r];
+    }
+    for (int e = tid; e < cur * t; e += kBeamThreads) {
+        const int j = e / t, p = e - j * t;
+        s_hist[j][p] = bans.hist[(size_t)(b * cur + j) * bans.hist_ld + p];
+    }
+    for (int c = tid; c < N; c += kBeamThreads) { c_valid[c] = 0; c_bank[c] = kInvalid; }
+    __syncthreads();
+
+    // the word that each history position bans by the n-gram rule (-1: none)
+    for (int e = tid; e < cur * t; e += kBeamThreads) {
+        const int j = e / t, p = e - j * t;
+        int64_t next = -1;
+        if (n >= 1 && p <= t - n) {
+            bool same = true;
+            for (int q = 0; q < n - 1; ++q) same = same && s_hist[j][p + q] == s_hist[j][t - n + 1 + q];
+            if (same) next = s_hist[j][p + n - 1];
+        }
+        s_next[j][p] = next;
+    }
+    // A: the k best of a live row among the entries that stage 1 left for it, each at the slot of its rank
+    for (int e = tid; e < n_ws; e += kBeamThreads) {
+        const int j = e / lists;
+        if (s_alive[j] == 0.f || w_idx[e] == kNone) continue;
+        int rank = 0;
+        for (int o = j * lists; o < (j + 1) * lists; ++o) rank += better(w_val[o], w_idx[o], w_val[e], w_idx[e]) ? 1 : 0;
+        if (rank < k) {
+            const int c = j * per + rank;
+            c_score[c] = w_val[e]; c_key[c] = w_idx[e]; c_valid[c] = 1;
+        }
+    }
+    __syncthreads();
+    // A of a finished row, and F: the forced words that the row may still choose
+    for (int c = tid; c < N; c += kBeamThreads) {
+        const int j = c / per, q = c - j * per;
+        const bool live = s_alive[j] != 0.f;
+        if (q < k) {
+            if (!live && q == 0) { c_score[c] = s_base[j]; c_key[c] = j * V; c_valid[c] = 1; }
+            continue;
+        }
+        const int64_t w = s_fw[q - k];
+        const int set = (q - k) / f.W;
+        if (!live || w < 0 || w >= V || ((s_met[j] >> set) & 1)) continue;
+        bool banned = w == eos && (bans.eos_word >= 0 || s_met[j] != full);
+        for (int i = 0; i < bans.n_sup; ++i) banned = banned || w == bans.sup[i];
+        if (bans.repeat_word && t >= 1) banned = banned || w == s_hist[j][t - 1];
+        for (int p = 0; p < t; ++p) banned = banned || w == s_next[j][p];
+        if (banned) continue;
+        c_score[c] = s_base[j] + logp.at((size_t)(b * cur + j) * ld + (int)w);
+        c_key[c] = j * V + (int)w;
+        c_valid[c] = 1;
+    }
+    __syncthreads();
+    // one candidate per (row, word); the sets that the word hits; the bank
+    for (int c = tid; c < N; c += kBeamThreads) {
+        if (!c_valid[c]) continue;
+        const int j = c / per, q = c - j * per;
+        bool dup = false;
+        if (q >= k)
+            for (int o = j * per; o < c; ++o) dup = dup || (c_valid[o] && c_key[o] == c_key[c]);
+        if (dup) continue;
+        int met = s_met[j];
+        if (s_alive[j] != 0.f) {
+            const int64_t w = c_key[c] - j * V;
+            for (int i = 0; i < CW; ++i)
+                if (s_fw[i] == w) met |= 1 << (i / f.W);
+        }
+        c_met[c] = met;
+        c_bank[c] = c_score[c] == -INFINITY ? -1 : __popc((unsigned)met);
+        // smaller = earlier under `better`: NaN above every number, value descending (-0 == +0), then the key ascending
+        const float v = c_score[c];
+        const unsigned bits = __float_as_uint(v == 0.f ? 0.f : v);
+        const unsigned descending = v != v ? 0u : ~((bits & 0x80000000u) ? ~bits : (bits | 0x80000000u));
+        c_ord[c] = ((uint64_t)descending << 32) | (unsigned)c_key[c];
+    }
+    __syncthreads();
+    for (int c = tid; c < N; c += kBeamThreads) {
+        const int bank = c_bank[c];
+        int slot = kNone;
+        if (bank != kInvalid) {
+            const uint64_t mine = c_ord[c];
+            int rank = 0;
+#pragma unroll 8
+            for (int o = 0; o < N; ++o) rank += (c_bank[o] == bank && c_ord[o] < mine) ? 1 : 0;
+            slot = (rank << 4) | (kMaxSets - bank);  // round by round, inside a round the high banks first
+        }
+        c_slot[c] = slot;
+    }
+    __syncthreads();
+    for (int c = tid; c < N; c += kBeamThreads) {
+        const int slot = c_slot[c];
+        if (slot == kNone) continue;
+        int pos = 0;
+#pragma unroll 8
+        for (int o = 0; o < N; ++o) pos += c_slot[o] < slot ? 1 : 0;
+        if (pos >= k) continue;
+        const int jb = c_key[c] / V, word = c_key[c] - jb * V;
+        const int row_id = b * cur + jb;
+        const size_t at = (size_t)b * k + pos;
+        sel_beam[at] = jb; sel_word[at] = word;
+        new_lp[at] = c_score[c]; new_mask[at] = s_alive[jb];
+        picked[at] = logp.at((size_t)row_id * ld + word) * s_alive[jb];
+        new_met[at] = c_met[c];
+    }
+}
+
 }  // namespace
 
 extern "C" long grit_beam_step_workspace(int B, int cur_beam, int k) {
@@ -569,6 +748,79 @@ extern "C" int grit_beam_step_div_f32(const float* const* maps, int n_maps, long
     return beam_step_rules(maps, n_maps, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, con, history,
                            history_ld, t, no_repeat_ngram, no_repeat_word, ban_eos, suppress, n_suppress, workspace, workspace_bytes,
                            sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, groups, diversity);
+}
+
+namespace {
+
+template <class Src>
+int beam_step_forced(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos,
+                     int first_step, int B, int cur_beam, int V, int k, const Bans& bans, const ForcedSets& sets, void* workspace,
+                     long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
+                     float* picked_logprob, int* new_met, void* stream) {
+    const int parts = cur_beam == 1 ? 8 : 2;
+    if ((long)cur_beam * V > 0x7fffffffL || B > 65535 || cur_beam * parts * k > 128 ||
+        (((V + parts - 1) / parts + 3) & ~3) > kMaxSlice)
+        return GRIT_ERR_UNSUPPORTED;
+    if (workspace_bytes < grit_beam_step_workspace(B, cur_beam, k)) return GRIT_ERR_BAD_ARG;
+    Forced<Src> part;
+    static_cast<Src&>(part) = src;
+    part.bans = bans;
+    part.forced = sets;
+    float* ws_val = reinterpret_cast<float*>(workspace);
+    int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)B * cur_beam * parts * kMaxK);
+    if (k <= 5)
+        hipLaunchKernelGGL((beam_partial<5, Forced<Src>>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part,
+                           ld, seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
+    else
+        hipLaunchKernelGGL((beam_partial<kMaxK, Forced<Src>>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream,
+                           part, ld, seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
+    hipLaunchKernelGGL(beam_forced_select<Src>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld, bans, sets, seq_logprob,
+                       seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word,
+                       new_seq_logprob, new_seq_mask, picked_logprob, new_met);
+    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int grit_beam_step_forced_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                                         const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                                         const int64_t* force_words, int n_sets, int n_words, const int* met_in,
+                                         const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
+                                         int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
+                                         int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
+                                         float* picked_logprob, int* new_met, void* stream) {
+    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V || !seq_logprob || !workspace || !sel_beam ||
+        !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob || !new_met || !force_words || n_sets < 1 || n_words < 1)
+        return GRIT_ERR_BAD_ARG;
+    if (!first_step && (!seq_mask || !prev_words)) return GRIT_ERR_BAD_ARG;
+    if (t < 0 || no_repeat_ngram < 0 || n_suppress < 0 || (n_suppress > 0 && !suppress) || (t > 0 && (!history || history_ld < t)) ||
+        (ban_eos && (eos < 0 || eos >= V)))
+        return GRIT_ERR_BAD_ARG;
+    if (n_maps > kMaxMaps || k > kMaxK || (cur_beam != 1 && cur_beam != k) || V < k || n_sets > kMaxSets || n_words > kMaxWords ||
+        t > kMaxHistory || n_suppress > kMaxSuppress)
+        return GRIT_ERR_UNSUPPORTED;
+    Bans bans{};
+    bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
+    bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
+    bans.n_sup = n_suppress;
+    for (int i = 0; i < n_suppress; ++i) {
+        if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
+        bans.sup[i] = suppress[i];
+    }
+    const ForcedSets sets{force_words, met_in, n_sets, n_words};
+    MeanMaps mean{};
+    for (int m = 0; m < n_maps; ++m) {
+        if (!maps[m]) return GRIT_ERR_BAD_ARG;
+        mean.t.p[m] = maps[m];
+    }
+    mean.n = n_maps;
+    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
+    mean.factor = (float)outputs / (float)(outputs * n_maps);
+    auto run = [&](auto src) {
+        return beam_step_forced(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, bans, sets, workspace,
+                                workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, new_met, stream);
+    };
+    return n_maps == 1 ? run(OneMap{maps[0]}) : run(mean);
 }
 
 extern "C" int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t* idx_out, float* val_out, void* stream) {

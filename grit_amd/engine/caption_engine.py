@@ -299,17 +299,20 @@ def consensus_reranker(consensus, text_field):
     return rerank
 
 
-def decode_consensus(model, samples, config, reranker):
+def decode_consensus(model, samples, config, reranker, force_words=None):
     """Decode model.consensus_candidates candidates per image as model.consensus_decode says ('beam': the N best final hypotheses
     of the configured search, constraints and groups honoured; 'sample': N samples) and keep the one that `reranker(tokens,
     log_probs)` chooses (DeviceCider.consensus, or consensus_reranker(...)).  Returns (tokens [B, 1, T], log_probs [B, 1, T]).
-    An Ensemble decodes 'beam' only and raises for 'sample', as it does anywhere."""
+    An Ensemble decodes 'beam' only and raises for 'sample', as it does anywhere.  force_words: the batch's sets of forced words
+    (Transformer.forward), for 'beam'; with 'sample' the model refuses them."""
     from grit_amd.config import consensus_options
     opt = consensus_options(config)
     n = opt['candidates']
     if n < 2:
         raise ValueError("decode_consensus needs model.consensus_candidates > 1")
     common = dict(seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx)
+    if force_words is not None:
+        common['force_words'] = force_words
     with torch.no_grad():
         if opt['decode'] == 'sample':
             tokens, log_probs = model(samples, beam_size=n, out_size=n, decode='sample', **opt['sample'], **common)
@@ -358,12 +361,13 @@ def evaluate_metrics(model, optimizers, dataloader, text_field, epoch=0, split='
     for it, batch in enumerate(_progress(dataloader, desc=f'Epoch {epoch} - evaluation on {split}', unit='it')):
         t0 = time.time()
         if rerank is not None:
-            out = decode_consensus(model, batch['samples'], config, rerank)[0][:, 0]
+            out = decode_consensus(model, batch['samples'], config, rerank, batch.get('force_words'))[0][:, 0]
         else:
+            forced = {} if batch.get('force_words') is None else dict(force_words=batch['force_words'])  # optional per batch
             with torch.no_grad():
                 out, _ = model(batch['samples'], seq=None, use_beam_search=True, max_len=config.model.beam_len,
                                eos_idx=config.model.eos_idx, beam_size=config.model.beam_size, out_size=1,
-                               return_probs=False, **beam_constraints(config), **beam_groups(config))
+                               return_probs=False, **beam_constraints(config), **beam_groups(config), **forced)
         if out.is_cuda:
             torch.cuda.synchronize()
         times.append(time.time() - t0)

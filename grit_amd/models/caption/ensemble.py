@@ -107,17 +107,29 @@ class Ensemble(BeamSearchSteps, nn.Module):
             raise ValueError("length_penalty must be >= 0, not %g" % length_penalty)
         # Transformer.forward's diverse search: taken out of kwargs like the rest, so that the search can still replay from a graph
         groups = beam_ops.groups(beam_size, kwargs.pop('num_groups', 1), kwargs.pop('diversity', 0.0))
+        # Transformer.forward's forced words: validated like the rest, refused with beam groups
+        first = self.models[0]
+        force_words = beam_ops.forced(first.cap_generator.fc.weight.shape[0], kwargs.pop('force_words', None), eos_idx, first.bos_idx,
+                                      getattr(first.config.model, 'pad_idx', None))
+        if force_words is not None and groups is not None:
+            raise NotImplementedError("forced words with beam groups are not built: use num_groups=1")
         if decode != 'beam':
             raise NotImplementedError("Ensemble only decodes by beam search: decode=%r is for a single Transformer (sampling from "
                                       "an average of distributions is not built)" % (decode,))
         self._check_placement()
         feats = self._member_features(samples)
+        if force_words is not None:
+            batch_size, device = self.get_bs_device(feats)
+            if force_words.shape[0] != batch_size:
+                raise ValueError("force_words names %d images, the batch has %d" % (force_words.shape[0], batch_size))
+            force_words = force_words.to(device)
         if self._graph_eligible(feats, return_probs, kwargs):
-            return self._beam_search_graphed(feats, max_len, eos_idx, beam_size, out_size, constraints, length_penalty, groups)
+            return self._beam_search_graphed(feats, max_len, eos_idx, beam_size, out_size, constraints, length_penalty, groups,
+                                             force_words)
         from grit_amd.ops.linear import suspend_single_use
         with suspend_single_use():
             return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
-                                           length_penalty=length_penalty, groups=groups, **kwargs)
+                                           length_penalty=length_penalty, groups=groups, force_words=force_words, **kwargs)
 
     def _graph_eligible(self, feats, return_probs, kwargs):
         if not _tr._GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
@@ -125,19 +137,24 @@ class Ensemble(BeamSearchSteps, nn.Module):
         _, device = self.get_bs_device(feats)
         return device.type == 'cuda' and not torch.cuda.is_current_stream_capturing()
 
-    def _beam_search_graphed(self, feats, max_len, eos_idx, beam_size, out_size, constraints=None, length_penalty=0.0, groups=None):
+    def _beam_search_graphed(self, feats, max_len, eos_idx, beam_size, out_size, constraints=None, length_penalty=0.0, groups=None,
+                             force_words=None):
         """`Transformer._beam_search_graphed` for K members: one graph per (every member's probe-parameter storage, batch, beam,
         length, constraints, beam groups, feature shapes), least recently used of 8 dropped, warm-up on a side stream.  The
-        members' own graph caches are not touched."""
+        members' own graph caches are not touched.  Forced words are a static device tensor that is rewritten before every replay;
+        only their shape is in the key."""
         def decode():
             return self._beam_search_eager([dict(s) for s in static_in], max_len, eos_idx, beam_size, out_size, False,
-                                           constraints=constraints, length_penalty=length_penalty, groups=groups)
+                                           constraints=constraints, length_penalty=length_penalty, groups=groups,
+                                           force_words=static_force)
 
         names = [sorted(k for k, v in f.items() if isinstance(v, torch.Tensor)) for f in feats]
         key = (max_len, eos_idx, beam_size, out_size, constraints, length_penalty, groups, torch.is_inference_mode_enabled(),
                feats[0][names[0][0]].device.index) + \
             tuple((p.data_ptr(), p.dtype) for m in self.models for p in self._probes(m)) + \
             tuple(tuple((k, tuple(f[k].shape), f[k].dtype) for k in n) for f, n in zip(feats, names))
+        if force_words is not None:
+            key += (('force_words', tuple(force_words.shape)),)
         entry = self._decode_graphs.pop(key, None)
         if entry is not None:
             self._decode_graphs[key] = entry  # most recently used last
@@ -147,6 +164,7 @@ class Ensemble(BeamSearchSteps, nn.Module):
             # every member reads its OWN static copy, also when the call hands all members the same tensors (one dict): the
             # graph must not depend on which members shared their inputs at capture time, since the key does not say
             static_in = [{k: f[k].clone() for k in n} for f, n in zip(feats, names)]
+            static_force = None if force_words is None else force_words.clone()
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
@@ -156,8 +174,10 @@ class Ensemble(BeamSearchSteps, nn.Module):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 static_out = decode()
-            entry = self._decode_graphs[key] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
+            entry = self._decode_graphs[key] = (graph, static_in, static_out, static_force)
+        graph, static_in, static_out, static_force = entry
+        if static_force is not None:
+            static_force.copy_(force_words)
         for f, s, n in zip(feats, static_in, names):
             for k in n:
                 if f[k].data_ptr() != s[k].data_ptr():
@@ -166,7 +186,7 @@ class Ensemble(BeamSearchSteps, nn.Module):
         return tuple(o.clone() for o in static_out)
 
     def _beam_search_eager(self, feats, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                           groups=None, **kwargs):
+                           groups=None, force_words=None, **kwargs):
         batch_size, device = self.get_bs_device(feats)
         self.seq_mask = torch.ones((batch_size, beam_size, 1), device=device)      # 1 while the beam is alive
         self.seq_logprob = torch.zeros((batch_size, 1, 1), device=device)          # running score per beam
@@ -174,6 +194,9 @@ class Ensemble(BeamSearchSteps, nn.Module):
         if return_probs:
             self.all_log_probs = []
         outputs = []
+        if force_words is not None:  # read by `iter` only when it is there
+            self.met = None
+            kwargs['force_words'] = force_words
         with ExitStack() as stack:
             for m in self.models:
                 stack.enter_context(_features_mode(m))
@@ -182,14 +205,15 @@ class Ensemble(BeamSearchSteps, nn.Module):
                 feats, outputs = self.iter(timestep=t, samples=feats, outputs=outputs, return_probs=return_probs,
                                            batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, constraints=constraints,
                                            groups=groups, **kwargs)
-        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty)
+        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty,
+                                 self.met if force_words is not None else None)
 
     def step(self, timestep, prev_output, samples, seq, mode='teacher_forcing', **kwargs):
         """Every member's word log-probabilities for this step (samples: one feature dict per member), [B * cur_beam, 1, V] each."""
         return [m.step(timestep, prev_output, f, seq, mode=mode, **kwargs) for m, f in zip(self.models, samples)]
 
     def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, groups=None,
-             **kwargs):
+             force_words=None, **kwargs):
         cur_beam = 1 if timestep == 0 else beam_size
         maps = [lp.view(batch_size, cur_beam, -1)
                 for lp in self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)]
@@ -198,10 +222,15 @@ class Ensemble(BeamSearchSteps, nn.Module):
             outputs = self._history(outputs)
         on_device = beam_ops.supported_mean(maps, cur_beam, beam_size) if groups is None else \
             beam_ops.supported_div(maps, cur_beam, beam_size, groups.num_groups)
+        if force_words is not None:
+            on_device = beam_ops.supported_forced(maps, cur_beam, beam_size)
         if _tr._FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if groups is not None:  # None beyond the kernel's limits, here and below: the composed form
+            if force_words is not None:  # None beyond the kernel's limits, here and below: the composed form
+                fused = beam_ops.beam_step_forced(maps, *state, force_words, self.met if timestep > 0 else None,
+                                                  outputs[0] if outputs else None, timestep, constraints)
+            elif groups is not None:
                 fused = beam_ops.beam_step_div(maps, *state, *groups, outputs[0] if outputs else None, timestep, constraints)
             elif constraints is None:
                 fused = beam_ops.beam_step_mean(maps, *state)
@@ -210,7 +239,7 @@ class Ensemble(BeamSearchSteps, nn.Module):
         if fused is None:
             word_logprob = torch.mean(torch.stack(maps), 0)
         outputs = self._beam_advance(self.models, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
-                                     eos_idx, constraints=constraints, groups=groups, **kwargs)
+                                     eos_idx, constraints=constraints, groups=groups, force_words=force_words, **kwargs)
         return samples, outputs
 
 

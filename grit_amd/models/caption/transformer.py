@@ -35,7 +35,8 @@ class BeamSearchSteps(object):
     seq_logprob, log_probs, selected_words (and all_log_probs) of the running search; `members` are the captioners whose
     registered states follow the surviving beams (the Transformer itself, or every model of an ensemble)."""
 
-    def _beam_result(self, outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx=None, length_penalty=0.0):
+    def _beam_result(self, outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx=None, length_penalty=0.0,
+                     met=None):
         outputs = torch.cat(outputs, -1)
         scores = self.seq_logprob
         if length_penalty != 0:
@@ -44,6 +45,11 @@ class BeamSearchSteps(object):
             length = torch.where(is_eos.any(-1), is_eos.long().argmax(-1) + 1, torch.full_like(outputs[..., 0], max_len))
             scores = scores / length.float().pow(float(length_penalty)).unsqueeze(-1)
         _, order = torch.sort(scores, 1, descending=True)
+        if met is not None:
+            # forced words: the hypotheses that met more sets first, inside a count by the score as before (met [B, beam] int32)
+            count = ((met.unsqueeze(-1) >> torch.arange(beam_ops.MAX_FORCED_SETS, device=met.device)) & 1).sum(-1)
+            _, by_count = torch.sort(torch.gather(count, 1, order.squeeze(-1)), dim=1, descending=True, stable=True)
+            order = torch.gather(order, 1, by_count.unsqueeze(-1))
         idx = order.expand(batch_size, beam_size, max_len)
         outputs = torch.gather(outputs, 1, idx)
         log_probs = torch.gather(torch.cat(self.log_probs, -1), 1, idx)
@@ -89,12 +95,23 @@ class BeamSearchSteps(object):
         return fn
 
     def _beam_advance(self, members, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size, eos_idx,
-                      constraints=None, groups=None, **kwargs):
+                      constraints=None, groups=None, force_words=None, **kwargs):
         """The body of `iter` after the word log-probabilities word_logprob [B, cur_beam, V]: `fused` holds what the fused step
         returned (sel_beam, sel_word, seq_logprob, seq_mask, picked), or is None for the composed torch form.  `constraints`
         (ops/beam.py) bans words per live beam; `outputs` then holds the history as one tensor (`_history`).  `groups`
-        (ops/beam.py: Groups) makes it the step of a diverse search, whose composed form is beam_step_groups_host."""
+        (ops/beam.py: Groups) makes it the step of a diverse search, whose composed form is beam_step_groups_host.  `force_words`
+        [B, C, W] makes it the step of a search with forced words: `fused` then ends with the new mask of met sets, which the search
+        object carries as `met` [B, beam] like seq_mask, and the composed form is beam_step_forced_host."""
         cur_beam = 1 if timestep == 0 else beam_size
+        if force_words is not None:
+            if fused is None:
+                state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None)
+                fused = beam_ops.beam_step_forced_host(word_logprob, *state, eos_idx, beam_size, force_words,
+                                                       self.met if timestep > 0 else None, outputs[0] if outputs else None, timestep,
+                                                       constraints)
+                if return_probs and timestep > 0:  # the plain composed form records the maps of finished beams as zeros
+                    word_logprob = word_logprob * (self.seq_mask * (self.selected_words.view(batch_size, cur_beam, 1) != eos_idx).float())
+            fused, self.met = fused[:5], fused[5]
         if fused is None and groups is not None:
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None)
             fused = beam_ops.beam_step_groups_host(word_logprob, *state, eos_idx, beam_size, *groups,
@@ -202,12 +219,15 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
 
     def forward(self, images, seq, use_beam_search=False, max_len=20, eos_idx=3, beam_size=5, out_size=1,
                 return_probs=False, decode='beam', temperature=1.0, top_k=0, top_p=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                no_repeat_word=False, suppress=(), length_penalty=0.0, num_groups=1, diversity=0.0, **kwargs):
+                no_repeat_word=False, suppress=(), length_penalty=0.0, num_groups=1, diversity=0.0, force_words=None, **kwargs):
         """Beam search under constraints (ops/beam.py): at least `min_len` words before <eos>, no n-gram of `no_repeat_ngram`
         words twice, no word twice in a row (`no_repeat_word`), the ids of `suppress` never; `length_penalty` = alpha ranks the
         final hypotheses by score / length^alpha.  All off by default.
         Diverse beam search: `num_groups` groups of beam_size / num_groups beams are searched in turn at every step, and a group
         pays `diversity` for every time a word was already chosen at this step by an earlier group; one group is the plain search.
+        Forced words: `force_words` [B, C, W] int64 padded with -1 names C sets of up to W word ids per image (ops/beam.py); the
+        beams are dealt out over banks by how many sets they have met, <eos> waits until a beam has met them all, and the final
+        hypotheses are ranked by the sets met, then by score.
         decode='sample' (with use_beam_search=True): `beam_size` independent samples per image from the word distribution at
         `temperature`, truncated to the `top_k` most probable words (0: all) and to the nucleus of mass `top_p`; `seed` is an
         integer, or None for a seed from torch's device generator.  Returns tokens and log-probs [B, out_size, max_len]."""
@@ -218,6 +238,15 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         if length_penalty < 0:
             raise ValueError("length_penalty must be >= 0, not %g" % length_penalty)
         groups = beam_ops.groups(beam_size, num_groups, diversity)
+        m = self.config.model
+        force_words = beam_ops.forced(self.cap_generator.fc.weight.shape[0], force_words, eos_idx, self.bos_idx,
+                                      getattr(m, 'pad_idx', None))
+        if force_words is not None:
+            if decode == 'sample':
+                raise NotImplementedError("decode='sample' draws independent samples: forced words are for decode='beam'")
+            if groups is not None:
+                raise NotImplementedError("forced words with beam groups are not built: use num_groups=1")
+            kwargs['force_words'] = force_words
         if decode == 'sample':
             if constraints is not None or length_penalty != 0:
                 raise NotImplementedError("decode='sample' takes no beam-search constraints and no length penalty")
@@ -233,20 +262,25 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
 
     # ------------------------------------------------------------------ beam search
     def beam_search(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                    groups=None, **kwargs):
+                    groups=None, force_words=None, **kwargs):
         """Inference on a HIP device (no autograd, eval mode): the decode loop -- grid net + `max_len` decoder steps + beam
         bookkeeping, ~5 000 small kernels whose launches bound the loop at ~2.7 ms of host time per step -- is captured ONCE per
         (batch, beam, length, feature shapes) into a HIP graph and replayed from then on (next-row N1: the device-side beam
         loop).  Same kernels, same order, same data: tokens and log-probs are those of the eager loop bit for bit.  Training
         (self-critical: beam search with gradient), CPU runs and return_probs keep the eager loop."""
+        if force_words is not None:
+            batch_size, device = self.get_bs_device(images)
+            if force_words.shape[0] != batch_size:
+                raise ValueError("force_words names %d images, the batch has %d" % (force_words.shape[0], batch_size))
+            force_words = force_words.to(device)
         if self._graph_eligible(images, return_probs, kwargs):
             vis = images if self.cached_features else self.detector(images)
             return self._beam_search_graphed(dict(vis), max_len, eos_idx, beam_size, out_size, constraints=constraints,
-                                             length_penalty=length_penalty, groups=groups)
+                                             length_penalty=length_penalty, groups=groups, force_words=force_words)
         from grit_amd.ops.linear import suspend_single_use
         with suspend_single_use():  # with gradient (self-critical training) the decoder's weights are used once per STEP
             return self._beam_search_eager(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
-                                           length_penalty=length_penalty, groups=groups, **kwargs)
+                                           length_penalty=length_penalty, groups=groups, force_words=force_words, **kwargs)
 
     def _graph_eligible(self, images, return_probs, kwargs):
         if not _GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
@@ -254,23 +288,24 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         _, device = self.get_bs_device(images)
         return device.type == 'cuda' and not torch.cuda.is_current_stream_capturing()
 
-    def _decode_from_features(self, vis, decode, static_seed):
+    def _decode_from_features(self, vis, decode, static_seed, static_force=None):
         was = self.cached_features
         self.cached_features = True
         try:
-            return decode(vis, static_seed)
+            return decode(vis, static_seed) if static_force is None else decode(vis, static_seed, static_force)
         finally:
             self.cached_features = was
 
     def _beam_search_graphed(self, vis, max_len, eos_idx, beam_size, out_size, sampling=None, seed=None, constraints=None,
-                             length_penalty=0.0, groups=None):
+                             length_penalty=0.0, groups=None, force_words=None):
         """sampling = (temperature, top_k, top_p) captures the sampled decode instead: part of the key, with the seed in a static
         device tensor that is rewritten from `seed` (a one-element device tensor) before every replay.  The constraint tuple, the
-        length penalty and the beam groups of a beam search are part of the key as well: they are baked into the captured launches."""
-        def decode(feats, static_seed):
+        length penalty and the beam groups of a beam search are part of the key as well: they are baked into the captured launches.
+        Forced words are data like the seed: a static device tensor that is rewritten before every replay, its shape in the key."""
+        def decode(feats, static_seed, static_force=None):
             if sampling is None:
                 return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, False, constraints=constraints,
-                                               length_penalty=length_penalty, groups=groups)
+                                               length_penalty=length_penalty, groups=groups, force_words=static_force)
             return self._sample_eager(feats, max_len, eos_idx, beam_size, out_size, *sampling, static_seed)
 
         names = sorted(k for k, v in vis.items() if isinstance(v, torch.Tensor))
@@ -282,6 +317,8 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
                torch.is_inference_mode_enabled(), vis[names[0]].device.index) + \
             tuple((p.data_ptr(), p.dtype) for p in probe) + \
             tuple((k, tuple(vis[k].shape), vis[k].dtype) for k in names)
+        if force_words is not None:
+            key += (('force_words', tuple(force_words.shape)),)
         entry = self._decode_graphs.pop(key, None)
         if entry is not None:
             self._decode_graphs[key] = entry  # most recently used last
@@ -290,19 +327,22 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
                 self._decode_graphs.pop(next(iter(self._decode_graphs)))  # least recently used one, not all of them
             static_in = {k: vis[k].clone() for k in names}
             static_seed = None if sampling is None else seed.clone()
+            static_force = None if force_words is None else force_words.clone()
             cur = torch.cuda.current_stream()
             side = torch.cuda.Stream()
             side.wait_stream(cur)
             with torch.cuda.stream(side):  # warm-up on a side stream: library workspaces, lazily built caches
-                self._decode_from_features(dict(static_in), decode, static_seed)
+                self._decode_from_features(dict(static_in), decode, static_seed, static_force)
             cur.wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = self._decode_from_features(dict(static_in), decode, static_seed)
-            entry = self._decode_graphs[key] = (graph, static_in, static_out, static_seed)
-        graph, static_in, static_out, static_seed = entry
+                static_out = self._decode_from_features(dict(static_in), decode, static_seed, static_force)
+            entry = self._decode_graphs[key] = (graph, static_in, static_out, static_seed, static_force)
+        graph, static_in, static_out, static_seed, static_force = entry
         if static_seed is not None:
             static_seed.copy_(seed)
+        if static_force is not None:
+            static_force.copy_(force_words)
         for k in names:
             if vis[k].data_ptr() != static_in[k].data_ptr():
                 static_in[k].copy_(vis[k])
@@ -310,7 +350,7 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         return tuple(o.clone() for o in static_out)
 
     def _beam_search_eager(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,
-                           groups=None, **kwargs):
+                           groups=None, force_words=None, **kwargs):
         batch_size, device = self.get_bs_device(images)
         self.seq_mask = torch.ones((batch_size, beam_size, 1), device=device)      # 1 while the beam is alive
         self.seq_logprob = torch.zeros((batch_size, 1, 1), device=device)          # running score per beam
@@ -318,12 +358,16 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         if return_probs:
             self.all_log_probs = []
         outputs = []
+        if force_words is not None:  # read by `iter` only when it is there: every other search passes what it always passed
+            self.met = None
+            kwargs['force_words'] = force_words
         with self._decode_session(batch_size):
             for t in range(max_len):
                 images, outputs = self.iter(timestep=t, samples=images, outputs=outputs, return_probs=return_probs,
                                             batch_size=batch_size, beam_size=beam_size, eos_idx=eos_idx, constraints=constraints,
                                             groups=groups, **kwargs)
-        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty)
+        return self._beam_result(outputs, batch_size, beam_size, max_len, out_size, return_probs, eos_idx, length_penalty,
+                                 self.met if force_words is not None else None)
 
     # ------------------------------------------------------------------ sampled decoding
     def sample_decode(self, images, max_len, eos_idx, n_samples, out_size, temperature, top_k, top_p, seed):
@@ -418,7 +462,7 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         return [layer.self_att for layer in self.cap_generator.layers]
 
     def iter(self, timestep, samples, outputs, return_probs, batch_size, beam_size=5, eos_idx=3, constraints=None, groups=None,
-             **kwargs):
+             force_words=None, **kwargs):
         cur_beam = 1 if timestep == 0 else beam_size
         word_logprob = self.step(timestep, self.selected_words, samples, None, mode='feedback', **kwargs)
         word_logprob = word_logprob.view(batch_size, cur_beam, -1)
@@ -427,18 +471,23 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
             outputs = self._history(outputs)
         on_device = beam_ops.supported(word_logprob, cur_beam, beam_size) if groups is None else \
             beam_ops.supported_div([word_logprob], cur_beam, beam_size, groups.num_groups)
+        if force_words is not None:
+            on_device = beam_ops.supported_forced([word_logprob], cur_beam, beam_size)
         if _FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
             # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py)
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if groups is not None:  # None beyond the kernel's limits, here and below: the composed form
+            if force_words is not None:  # None beyond the kernel's limits, here and below: the composed form
+                fused = beam_ops.beam_step_forced([word_logprob], *state, force_words, self.met if timestep > 0 else None,
+                                                  outputs[0] if outputs else None, timestep, constraints)
+            elif groups is not None:
                 fused = beam_ops.beam_step_div([word_logprob], *state, *groups, outputs[0] if outputs else None, timestep, constraints)
             elif constraints is None:
                 fused = beam_ops.beam_step(word_logprob, *state)
             else:
                 fused = beam_ops.beam_step_con([word_logprob], *state, outputs[0] if outputs else None, timestep, constraints)
         outputs = self._beam_advance((self,), timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
-                                     eos_idx, constraints=constraints, groups=groups, **kwargs)
+                                     eos_idx, constraints=constraints, groups=groups, force_words=force_words, **kwargs)
         return samples, outputs
 
     def _follow_beams(self, selected_beam, cur_beam, batch_size, beam_size):

@@ -2,8 +2,9 @@
 candidate scores, top-k over beam x vocabulary, beam / word split and the score / mask / log-prob gathers of the reference's
 Transformer.iter (models/caption/transformer.py:208-240), bit-identical to the composed torch form.  `beam_step_mean` is the same
 step for an ensemble (models/caption/ensemble.py:128-214): the average of the members' maps (grit_beam_step_mean_f32).  Past the
-reference: the step under constraints (grit_beam_step_con_f32) and the step of a diverse search over beam groups
-(grit_beam_step_div_f32), each with its host form in torch ops."""
+reference: the step under constraints (grit_beam_step_con_f32), the step of a diverse search over beam groups
+(grit_beam_step_div_f32) and the step of a search with forced words (grit_beam_step_forced_f32), each with its host form in
+torch ops."""
 import collections
 import ctypes
 
@@ -351,3 +352,216 @@ def beam_step_div(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, bea
         return None
     _lib.check(st, "grit_beam_step_div_f32")
     return sel_beam, sel_word, new_lp, new_mask, picked
+
+
+# ------------------------------------------------------------------------------------------------------ forced words
+# Constrained beam search by dynamic beam allocation (Post & Vilar 2018; the force_words_ids of the generation libraries).
+# force_words [B, C, W] int64 padded with -1: set c of image b is the ids >= 0 of force_words[b, c], a disjunction ("dog" or
+# "dogs"); a set with no ids counts as met from the start.  Every beam carries `met`, an int32 bitmask of the sets that its words
+# so far have hit; full = all C bits.  One step for an image with `cur` source rows and k = beam_size:
+#   1. a live row has the bans of the constrained step, and <eos> is banned in addition while met != full;
+#   2. candidates A: row j contributes its k best candidates under the constrained step's scoring (live: seq_logprob[j] +
+#      logp[j][w], -inf where banned, ties to the ascending word); a finished row only its word-0 candidate, score seq_logprob[j];
+#   3. candidates F: a live row also contributes (j, w) for every w of a set that it has not met and that is not banned for it,
+#      same single add; duplicates of (j, w) are kept once;
+#   4. met'(j, w) = met[j] | {c : w in set c} for a live row, met[j] for a finished one; bank = popcount(met'); a candidate that
+#      scores -inf goes to bank -1;
+#   5. inside a bank: score descending, then j * V + w ascending;
+#   6. for round r = 0, 1, 2, ... and within a round for bank = C down to -1: a bank with more than r candidates gives its r-th,
+#      until k are chosen;
+#   7. outputs in the order of choice: sel_beam, sel_word, the candidate's score, the source row's liveness, the stored log-prob
+#      times liveness, and new_met = met'.
+# `beam_step_forced_host` states this in torch ops; grit_beam_step_forced_f32 is the same on the device in two launches.
+MAX_FORCED_SETS, MAX_FORCED_WORDS = _lib.BEAM_MAX_FORCED_SETS, _lib.BEAM_MAX_FORCED_WORDS
+
+
+def forced(V, force_words, eos_idx, bos_idx=None, pad_idx=None):
+    """The validated force_words of one search over a vocabulary of V words: an int64 tensor [B, C, W] padded with -1 (a tensor or
+    nested lists of that shape), or None when there is nothing to force (None, C == 0 or W == 0).  ValueError for ids >= V, for
+    <eos> / <bos> / <pad> in a set, for more than 8 sets or more than 4 words in a set."""
+    if force_words is None:
+        return None
+    fw = torch.as_tensor(force_words)
+    if fw.dim() != 3 or fw.dtype.is_floating_point or fw.dtype == torch.bool:
+        raise ValueError("force_words must be an integer tensor [B, sets, words] padded with -1, not %s %s"
+                         % (fw.dtype, tuple(fw.shape)))
+    B, C, W = fw.shape
+    if C > MAX_FORCED_SETS:
+        raise ValueError("%d sets of forced words: at most %d" % (C, MAX_FORCED_SETS))
+    if W > MAX_FORCED_WORDS:
+        raise ValueError("%d words in a set of forced words: at most %d" % (W, MAX_FORCED_WORDS))
+    if fw.numel() == 0:
+        return None
+    fw = fw.long().contiguous()
+    special = [(name, i) for name, i in (("<eos>", eos_idx), ("<bos>", bos_idx), ("<pad>", pad_idx)) if i is not None and i >= 0]
+    # one read of the device for all checks: the largest id, then how often every special id occurs
+    top, *found = torch.stack([fw.max()] + [(fw == i).sum() for _, i in special]).tolist()
+    if top >= V:
+        raise ValueError("forced word %d is outside the vocabulary [0, %d)" % (top, V))
+    for (name, i), bad in zip(special, found):
+        if bad:
+            raise ValueError("%s (%d) cannot be a forced word" % (name, i))
+    return fw
+
+
+def initial_met(force_words):
+    """int32 [B]: the mask of the sets of every image that hold no id, which count as met from the start."""
+    C = force_words.shape[1]
+    bits = 1 << torch.arange(C, dtype=torch.int32, device=force_words.device)
+    return ((force_words < 0).all(-1).int() * bits).sum(-1, dtype=torch.int32)
+
+
+def beam_step_forced_host(word_logprob, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, force_words, met=None, history=None,
+                          t=0, con=None):
+    """The step with forced words in torch ops, on any device and with gradient: the arguments of `beam_step` (word_logprob is the
+    mean already for an ensemble), force_words [B, C, W], met [B, cur_beam] int32 (None: the first step, the empty sets), and the
+    history / step / constraint tuple of `beam_step_con`.  Returns what `beam_step` returns and new_met [B, beam] int32."""
+    B, cur, V = word_logprob.shape
+    k, dev = beam_size, word_logprob.device
+    C, W = force_words.shape[1], force_words.shape[2]
+    if cur not in (1, k) or V < k or force_words.shape[0] != B:
+        raise ValueError("forced words over %d beams with %d source rows of %d words, %d images" % (k, cur, V, force_words.shape[0]))
+    seq_logprob = seq_logprob.reshape(B, cur, 1)
+    if prev_words is None:
+        alive = torch.ones((B, cur, 1), dtype=torch.float32, device=dev)
+    else:
+        alive = seq_mask.reshape(B, cur, 1) * (prev_words.reshape(B, cur, 1) != eos_idx).float()
+    live = alive != 0  # [B, cur, 1]
+    full = (1 << C) - 1
+    met = initial_met(force_words).view(B, 1).expand(B, cur) if met is None else met.reshape(B, cur).int()
+    # 1. bans
+    if con is not None:
+        if history is None:
+            history = torch.zeros((B, cur, 0), dtype=torch.long, device=dev)
+        banned = banned_words_host(history, None if prev_words is None else alive, t, eos_idx, V, **con._asdict())
+    else:
+        banned = torch.zeros((B, cur, V), dtype=torch.bool, device=dev)
+    if 0 <= eos_idx < V:
+        banned[:, :, eos_idx] |= live[:, :, 0] & (met != full)
+    cand = (seq_logprob + word_logprob).masked_fill(banned, float('-inf'))
+    # 2. A: k per live row, the word-0 candidate of a finished row
+    a_score, a_word = torch.sort(cand, dim=-1, descending=True, stable=True)
+    a_score, a_word = a_score[:, :, :k], a_word[:, :, :k]
+    a_valid = live | (torch.arange(k, device=dev) == 0)
+    a_word = torch.where(live, a_word, torch.zeros_like(a_word))
+    a_score = torch.where(live, a_score, seq_logprob.expand(B, cur, k))
+    # 3. F: the words of the sets that a live row has not met, unless banned for it
+    fw = force_words.reshape(B, 1, C * W).expand(B, cur, C * W)
+    set_of = torch.arange(C, device=dev).repeat_interleave(W)
+    unmet = ((met.unsqueeze(-1) >> set_of) & 1) == 0
+    f_word = fw.clamp(min=0)
+    f_valid = (fw >= 0) & unmet & live & ~torch.gather(banned, 2, f_word)
+    f_score = seq_logprob + torch.gather(word_logprob, 2, f_word)
+    n = k + C * W
+    valid = torch.cat([a_valid, f_valid], -1).reshape(B, cur * n)
+    word = torch.cat([a_word, f_word], -1)
+    score = torch.cat([a_score, f_score], -1).reshape(B, cur * n)
+    row = torch.arange(cur, device=dev).view(1, cur, 1).expand(B, cur, n)
+    key = (row * V + word).reshape(B, cur * n)
+    row, word = row.reshape(B, cur * n), word.reshape(B, cur * n)
+    N = cur * n
+    earlier = torch.ones((N, N), dtype=torch.bool, device=dev).tril(-1)  # [i, o]: o < i
+    valid = valid & ~((key.unsqueeze(2) == key.unsqueeze(1)) & valid.unsqueeze(1) & earlier).any(-1)
+    # 4. banks
+    in_set = ((word.view(B, N, 1, 1) == force_words.view(B, 1, C, W)) & (force_words.view(B, 1, C, W) >= 0)).any(-1)  # [B, N, C]
+    hits = (in_set.int() * (1 << torch.arange(C, dtype=torch.int32, device=dev))).sum(-1, dtype=torch.int32)
+    row_met, row_live = torch.gather(met, 1, row), torch.gather(live[:, :, 0], 1, row)
+    new_met = torch.where(row_live, row_met | hits, row_met)
+    bank = sum((new_met >> c) & 1 for c in range(C))
+    bank = torch.where(score == float('-inf'), torch.full_like(bank, -1), bank)
+    bank = torch.where(valid, bank, torch.full_like(bank, -2))
+    # 5. the candidates bank by bank (descending), inside a bank by score descending, then key ascending
+    order = torch.sort(key, dim=1, stable=True)[1]
+    order = torch.gather(order, 1, torch.sort(torch.gather(score.detach(), 1, order), dim=1, descending=True, stable=True)[1])
+    order = torch.gather(order, 1, torch.sort(torch.gather(bank, 1, order), dim=1, descending=True, stable=True)[1])
+    # 6. round r takes the r-th of every bank, high banks first: a stable sort by the rank inside the bank
+    sorted_bank = torch.gather(bank, 1, order)
+    at = torch.arange(N, device=dev).expand(B, N)
+    starts = torch.ones((B, N), dtype=torch.bool, device=dev)
+    starts[:, 1:] = sorted_bank[:, 1:] != sorted_bank[:, :-1]
+    rank = at - torch.cummax(torch.where(starts, at, torch.zeros_like(at)), 1)[0]
+    rank = torch.where(sorted_bank == -2, torch.full_like(rank, N), rank)
+    chosen = torch.gather(order, 1, torch.sort(rank, dim=1, stable=True)[1][:, :k])
+    # 7. outputs
+    sel_beam, sel_word = torch.gather(row, 1, chosen), torch.gather(word, 1, chosen)
+    col = sel_beam.unsqueeze(-1)
+    new_mask = torch.gather(alive, 1, col)
+    picked = torch.gather(torch.gather(word_logprob, 1, col.expand(B, k, V)), 2, sel_word.unsqueeze(-1)) * new_mask
+    return sel_beam, sel_word, torch.gather(score, 1, chosen).unsqueeze(-1), new_mask, picked, torch.gather(new_met, 1, chosen)
+
+
+def supported_forced(word_logprobs, cur_beam, beam_size):
+    """The step with forced words runs on the device kernel: what `supported_mean` asks of the maps, one or beam_size source rows
+    and a vocabulary of at least beam_size words."""
+    return (supported_mean(word_logprobs, cur_beam, beam_size) and cur_beam in (1, beam_size)
+            and word_logprobs[0].shape[-1] >= beam_size)
+
+
+def beam_step_forced(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, force_words, met=None, history=None, t=0,
+                     con=None):
+    """The step with forced words of one map or of the mean of several on the device (grit_beam_step_forced_f32: two launches,
+    nothing uploaded): force_words [B, C, W] int64 and met [B, cur_beam] int32 (None: the first step) are device tensors.  Returns
+    the five outputs of `beam_step` and new_met [B, beam] int32, or None when the call is outside the kernel's limits (a beam above
+    8, fewer words than beams, more than 8 sets or 4 words a set, and the limits of `beam_step_con`): the caller uses
+    `beam_step_forced_host`."""
+    B, cur, V = word_logprobs[0].shape
+    C, W = force_words.shape[1], force_words.shape[2]
+    if beam_size > 8 or V < beam_size or cur not in (1, beam_size) or len(word_logprobs) > MAX_MAPS:
+        return None
+    if not (1 <= C <= MAX_FORCED_SETS and 1 <= W <= MAX_FORCED_WORDS):
+        return None
+    if con is not None and (t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS):
+        return None
+    # the kernel reads evenly spaced rows of adjacent words (any row stride >= V); every other layout is copied
+    ld = {m.stride(0) if cur == 1 else m.stride(1) for m in word_logprobs}
+    spaced = len(ld) == 1 and min(ld) >= V and all(m.stride(2) == 1 and (cur == 1 or m.stride(0) == cur * m.stride(1))
+                                                   for m in word_logprobs)
+    maps = list(word_logprobs) if spaced else [m.contiguous() for m in word_logprobs]
+    ld = min(ld) if spaced else V
+    first = prev_words is None
+    dev = maps[0].device
+    if force_words.shape[0] != B or force_words.dtype != torch.int64 or force_words.device != dev:
+        raise _lib.GritHipError("force_words must be int64 [%d, sets, words] on %s" % (B, dev))
+    fw = force_words if force_words.is_contiguous() else force_words.contiguous()
+    if met is not None:
+        if met.numel() != B * cur or met.dtype != torch.int32 or met.device != dev:
+            raise _lib.GritHipError("met must be int32 with %d x %d entries on %s" % (B, cur, dev))
+        met = met.reshape(-1).contiguous()
+    L = _lib.load()
+    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
+    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
+    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
+    new_met = torch.empty((B, beam_size), dtype=torch.int32, device=dev)
+    slp = seq_logprob.reshape(-1).float().contiguous()
+    if slp.numel() != B * cur:
+        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
+    sm = pw = hist = None
+    if not first:
+        sm = seq_mask.reshape(-1).float().contiguous()
+        pw = prev_words.reshape(-1).contiguous()
+        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
+            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
+    if con is None:
+        con, t = Constraints(0, 0, False, ()), 0
+    if t > 0:
+        hist = history.reshape(B * cur, -1)
+        if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
+            raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
+        hist = hist if hist.stride(1) == 1 else hist.contiguous()
+    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host arrays: passed by value to the kernel
+    ids = (ctypes.c_int * max(1, len(con.suppress)))(*con.suppress)
+    with _lib.device_guard(dev):
+        st = L.grit_beam_step_forced_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), ld, _ptr(slp), _ptr(sm), _ptr(pw),
+                                         int(eos_idx), int(first), B, cur, V, beam_size, _ptr(fw), C, W, _ptr(met), _ptr(hist),
+                                         hist.stride(0) if hist is not None else 0, int(t), con.no_repeat_ngram,
+                                         int(con.no_repeat_word), int(t < con.min_len), ctypes.cast(ids, ctypes.c_void_p),
+                                         len(con.suppress), _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp),
+                                         _ptr(new_mask), _ptr(picked), _ptr(new_met), _lib.current_stream_ptr())
+    if st == _lib.ERR_UNSUPPORTED:
+        return None
+    _lib.check(st, "grit_beam_step_forced_f32")
+    return sel_beam, sel_word, new_lp, new_mask, picked, new_met

@@ -51,6 +51,8 @@
  *                           with a per-beam set of banned words applied while the candidates are scored
  *   grit_beam_step_div_f32 <- nothing in the reference (its beams are near-copies of one sentence): the same step for beam groups
  *                           that are searched in turn, a group paying for every word an earlier group chose at this step
+ *   grit_beam_step_forced_f32 <- nothing in the reference (its search cannot be made to mention a word): the same step with sets of
+ *                           forced words per image, the beams of a step dealt out over banks by how many sets they have met
  *   grit_sample_step_f32 <- nothing in the reference (it decodes by beam search only): one word per row drawn from the tempered,
  *                           top-k / nucleus truncated word distribution, in integer arithmetic that a host form repeats exactly
  *   grit_decode_step_inputs <- CaptionGenerator.get_seq_inputs in stateful mode + the word / position embedding sum
@@ -69,7 +71,7 @@
  *   grit_jpeg_probe, grit_jpeg_entropy, grit_jpeg_reconstruct
  *                        <- PIL's Image.open(path).convert('RGB') in the dataset workers (datasets/caption/field.py:65,
  *                           tools/extract_features.py:42): libjpeg-turbo's baseline decode at its defaults
- * (none of the last seventeen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ * (none of the last eighteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
  *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
@@ -81,7 +83,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 58
+#define GRIT_ABI_VERSION 59
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -859,6 +861,53 @@ int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const 
                            int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
                            int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * The beam-search step with FORCED words (dynamic beam allocation, Post & Vilar 2018; no ancestor in the reference).
+ * force_words [B, n_sets, n_words] int64, padded with -1, lives on the device: set c of image b is the ids >= 0 of
+ * force_words[b][c], a disjunction ("dog" or "dogs"); a set with no ids counts as met from the start.  Every beam carries met, an
+ * int32 bitmask of the sets that its words so far have hit; full = all n_sets bits.  met_in [B * cur_beam] may be NULL (the first
+ * step): every row of image b then starts from the mask of b's empty sets.  A step for an image with cur_beam source rows and
+ * k = beam, liveness of a row exactly that of grit_beam_step_con_f32:
+ *   1. Bans.  A live row has the bans of grit_beam_step_con_f32 (ban_eos, suppress, no_repeat_word, no_repeat_ngram), and <eos>
+ *      is banned in addition while met != full.
+ *   2. Candidates A.  Row j contributes its k best candidates under the constrained step's scoring: a live row scores
+ *      seq_logprob[j] + logp[j][w] (one fp32 add; -inf where banned), ties to the ascending word -- what stage 1 of that step
+ *      leaves in the workspace.  A finished row contributes only its word-0 candidate with the score seq_logprob[j]; its -999
+ *      siblings are not candidates here.
+ *   3. Candidates F.  A live row j also contributes (j, w) for every w of a set that row j has not met and that is not banned for
+ *      that row, scored by the same single add (for n_maps > 1 on the mean re-formed exactly as grit_beam_step_mean_f32 forms
+ *      it).  Duplicates of (j, w) are kept once; their scores are identical bits.
+ *   4. Banks.  met'(j, w) = met[j] | {c : w in set c} for a live row, met[j] for a finished row; bank = popcount(met'); a
+ *      candidate that scores -inf goes to bank -1.
+ *   5. Inside a bank the candidates are ordered by score descending, then by j * V + w ascending.
+ *   6. Slots.  For round r = 0, 1, 2, ... and within a round for bank = n_sets down to -1: if the bank has more than r candidates
+ *      and fewer than k are chosen, choose its r-th.  (There are always at least k candidates: k from row 0 at the first step,
+ *      later at least one per row.)
+ *   7. Outputs, at the position given by the order of choice: sel_beam, sel_word, new_seq_logprob = the candidate's score,
+ *      new_seq_mask = the source row's liveness, picked_logprob = the stored log-prob * liveness as in the other steps, and
+ *      new_met [B, k] int32 = met'.
+ * By construction the top candidate of the highest non-empty bank gets a slot at every step and banks only grow, so with at least
+ * n_sets steps and no forced word under a ban the best hypothesis of the top bank holds a word of every set; that it also reaches
+ * <eos> is not promised.  The host form is grit_amd/ops/beam.py: beam_step_forced_host.
+ *
+ * Stage 1 is the first launch of grit_beam_step_con_f32 (k entries per list) with the one per-row addition of the <eos> ban;
+ * stage 2 is one workgroup per image over at most cur_beam * (k + n_sets * n_words) <= 320 candidates in LDS: it gathers the
+ * forced candidates from logp, tests them against the row's ban rules, removes duplicates, banks, ranks and stores.  Workspace:
+ * grit_beam_step_workspace(B, cur_beam, k).  Limits (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form): k <= 8,
+ * cur_beam == 1 or cur_beam == k, V >= k, n_sets <= GRIT_BEAM_MAX_FORCED_SETS, n_words <= GRIT_BEAM_MAX_FORCED_WORDS, and the
+ * limits of grit_beam_step_con_f32.  n_sets < 1, n_words < 1 or force_words / new_met == NULL: GRIT_ERR_BAD_ARG.  Forced ids
+ * outside [0, V) are skipped.  Two launches, no atomics on global memory, no host state, nothing uploaded; safe to capture in a
+ * HIP graph.
+ * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_BEAM_MAX_FORCED_SETS 8
+#define GRIT_BEAM_MAX_FORCED_WORDS 4
+int grit_beam_step_forced_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
+                              const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
+                              const int64_t* force_words, int n_sets, int n_words, const int* met_in, const int64_t* history,
+                              long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos, const int* suppress,
+                              int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
+                              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, int* new_met, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * One step of sampled decoding after the decoder (no ancestor in the reference, whose only decoder is beam search): one word per

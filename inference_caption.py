@@ -3,6 +3,7 @@
 
     python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth [ckpt2.pth ...]] [--vocab data/vocab.json] [--beam 5]
                                 [--groups G --diversity X] [--n-best N] [--sample N] [--consensus --consensus-corpus captions.json]
+                                [--force "dog|dogs" frisbee]
 
 Several checkpoints: one model per checkpoint, captioned together by models.caption.ensemble.Ensemble (their word
 log-probabilities averaged at every beam step).
@@ -15,7 +16,7 @@ import os
 
 import torch
 
-from grit_amd.config import beam_constraints, beam_groups, default_config
+from grit_amd.config import beam_constraints, beam_groups, default_config, force_words_ids
 from grit_amd.tuning import load_tuned_gemms
 from models.caption import Transformer
 from models.caption.detector import build_detector
@@ -45,14 +46,23 @@ def build_captioner(config, device, checkpoints=('',)):
 
 
 @torch.inference_mode()
-def caption_tokens(model, image, config, beam_size=None, n_best=1):
+def caption_tokens(model, image, config, beam_size=None, n_best=1, force_words=None):
     """image [3,H,W] (already normalised) -> (tokens [1, beam_len] int64, log_probs [1, beam_len]); with n_best > 1 the n_best
-    best final hypotheses, [1, n_best, beam_len] each."""
+    best final hypotheses, [1, n_best, beam_len] each.  force_words [1, sets, words] (config.force_words_ids): the caption holds a
+    word of every set."""
     device = next(model.parameters()).device
     images = nested_tensor_from_tensor_list([image]).to(device)
+    forced = {} if force_words is None else dict(force_words=force_words)
     return model(images, seq=None, use_beam_search=True, max_len=config.model.beam_len, eos_idx=config.model.eos_idx,
                  beam_size=beam_size or config.model.beam_size, out_size=n_best, return_probs=False, **beam_constraints(config),
-                 **beam_groups(config))
+                 **beam_groups(config), **forced)
+
+
+def vocabulary(vocab_path):
+    """The words of vocab.json in id order."""
+    with open(vocab_path) as f:
+        vocab = json.load(f)
+    return vocab['itos'] if isinstance(vocab, dict) and 'itos' in vocab else vocab
 
 
 @torch.inference_mode()
@@ -181,6 +191,8 @@ def build_parser():
     ap.add_argument('--groups', type=int, default=1, metavar='G', help="diverse beam search: G groups of beam / G beams (1: off)")
     ap.add_argument('--diversity', type=float, default=0.0, metavar='X',
                     help="what a group pays per earlier choice of the same word at a step")
+    ap.add_argument('--force', nargs='*', default=[], metavar='WORDS',
+                    help='words that the caption must mention: one set per argument, alternatives separated by | ("dog|dogs" frisbee)')
     ap.add_argument('--n-best', type=int, default=1, metavar='N', help="print the N best final hypotheses instead of one")
     ap.add_argument('--sample', type=int, default=0, metavar='N', help="print N sampled captions instead of the best beam")
     ap.add_argument('--temperature', type=float, default=1.0)
@@ -202,6 +214,10 @@ def parse_args(argv=None):
         ap.error("--consensus needs --consensus-corpus FILE (the captions the CIDEr-D document frequencies come from)")
     if a.consensus and max(a.n_best, a.sample) < 2:
         ap.error("--consensus reranks several candidates: give --n-best N or --sample N with N > 1")
+    if a.force and a.sample > 0:
+        ap.error("--force steers the beam search: it does not go with --sample")
+    if a.force and a.groups > 1:
+        ap.error("--force does not go with --groups")
     return a
 
 
@@ -233,7 +249,9 @@ def run_main():
     config = default_config(**{'model.beam_min_len': a.min_len, 'model.beam_no_repeat_ngram': a.no_repeat_ngram,
                                'model.beam_no_repeat_word': a.no_repeat_word, 'model.beam_suppress': list(a.suppress),
                                'model.beam_length_penalty': a.length_penalty, 'model.beam_groups': a.groups,
-                               'model.beam_diversity': a.diversity})
+                               'model.beam_diversity': a.diversity, 'model.beam_force_words': list(a.force)})
+    # words -> ids before anything is built: an unknown word is an error that names it
+    force_words = force_words_ids(config.model.beam_force_words, vocabulary(a.vocab)) if a.force else None
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
     model = build_captioner(config, device, a.checkpoint)
     if a.img.endswith('.npy'):
@@ -250,7 +268,7 @@ def run_main():
         if a.sample > 0:
             tokens, _ = sample_tokens(model, image, config, a.sample, a.temperature, a.top_k, a.top_p, a.seed)
         else:
-            tokens = caption_tokens(model, image, config, a.beam, a.n_best)[0][0]
+            tokens = caption_tokens(model, image, config, a.beam, a.n_best, force_words)[0][0]
         print_consensus(tokens, cider, a.vocab, config.model.eos_idx)
         return
     if a.sample > 0:
@@ -258,7 +276,7 @@ def run_main():
         for line in (decode(tokens, a.vocab, config.model.eos_idx) if os.path.exists(a.vocab) else tokens.tolist()):
             print(line)
         return
-    tokens, _ = caption_tokens(model, image, config, a.beam, a.n_best)
+    tokens, _ = caption_tokens(model, image, config, a.beam, a.n_best, force_words)
     if a.n_best == 1:
         print(decode(tokens, a.vocab, config.model.eos_idx)[0] if os.path.exists(a.vocab) else tokens.tolist())
         return
