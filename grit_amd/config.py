@@ -34,6 +34,8 @@ def to_config(obj):
 
 _DEFAULTS = {
     'exp': dict(seed=42, name='eval', rank=0, ngpus_per_node=8, world_size=8, checkpoint='', eval=False, resume=False,
+                # the validation loss of every epoch (engine.caption_engine.evaluate_loss): 'torch' = model(samples, captions) + NLLLoss as in the reference; 'fused' = model.score (the likelihood head of grit_amd/ops/vocab_score.py: no [rows, V] map)
+                eval_loss_head='torch',
                 eval_scorer='device'),  # the per-epoch BLEU / ROUGE / CIDEr of train_caption.main: 'device' scores the beam tokens in one kernel launch (grit_amd/ops/caption_scores.py), 'host' decodes and scores in Python as the reference does (the choice for a run without a GPU: 'device' is refused there)
     'dataset': dict(overfit=False, ann_root='', img_root='', hdf5_path='', vocab_path='',
                     use_gri_feat=True, use_reg_feat=True,

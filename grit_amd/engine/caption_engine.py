@@ -127,17 +127,50 @@ def xe_loss(model, batch, loss_fn):
     return loss_fn(out.view(-1, out.shape[-1]), target.view(-1))
 
 
-def evaluate_loss(model, dataloader, loss_fn, text_field, epoch, writer):
+def score_captions(model, samples, captions, normalize=None):
+    """How likely `model` (a Transformer or an Ensemble, wrapped or not) finds `captions` [B, T] or [B, N, T] for `samples`:
+    CaptionScores(log_probs, total, length) of models/caption/transformer.py.  Eval mode, no autograd."""
+    net = _unwrap(model)
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            return net.score(samples, captions, normalize=normalize)
+    finally:
+        net.train(was_training)
+
+
+def fused_xe_loss(model, batch, pad_idx):
+    """xe_loss from the likelihood head: NLLLoss(ignore_index=pad, reduction='mean') = -sum of the non-pad targets' log-probs /
+    their number, without the [rows, V] map.  The model's pad index must be the loss's."""
+    net = _unwrap(model)
+    if net.cap_generator.pad_idx != pad_idx:
+        raise ValueError("head='fused' ignores the model's pad index %d, the loss ignores %d" % (net.cap_generator.pad_idx, pad_idx))
+    scores = net.score(batch['samples'], batch['captions'])
+    return -scores.log_probs.sum() / scores.length.sum()
+
+
+def evaluate_loss(model, dataloader, loss_fn, text_field, epoch, writer, head='torch'):
+    """head='torch': the reference's loop.  head='fused': the same loss per batch from model.score (ops/vocab_score.py)."""
+    if head not in ('torch', 'fused'):
+        raise ValueError("head must be 'torch' or 'fused', not %r" % (head,))
     model.eval()
     running = .0
     with torch.no_grad():
         for it, batch in enumerate(_progress(dataloader, desc='Epoch %d - validation' % epoch, unit='it')):
-            loss = gather_result(xe_loss(model, batch, loss_fn))
+            if head == 'fused':
+                loss = gather_result(fused_xe_loss(model, batch, loss_fn.ignore_index))
+            else:
+                loss = gather_result(xe_loss(model, batch, loss_fn))
             running += loss.item()
     val_loss = running / max(1, len(dataloader))
     if writer is not None and get_rank() == 0:
         writer.add_scalar('val_loss', val_loss, epoch)
     return val_loss
+
+
+def _eval_loss_head(config):
+    return getattr(getattr(config, 'exp', None), 'eval_loss_head', 'torch') or 'torch'
 
 
 def train_xe_step(model, batch, optimizers, loss_fn, scheduler=None, autocast_dtype=None, gather=True):
@@ -232,7 +265,7 @@ def train_xe(model, dataloaders, optimizers, text_field, epoch, rank=0, config=N
             writer.add_scalar('backbone_lr', optimizers['backbone'].param_groups[0]['lr'], epoch * n + it)
             writer.add_scalar('model_lr', optimizers['model'].param_groups[0]['lr'], epoch * n + it)
     _consolidate(model)
-    val_loss = evaluate_loss(model, dataloaders['valid'], loss_fn, text_field, epoch, writer) \
+    val_loss = evaluate_loss(model, dataloaders['valid'], loss_fn, text_field, epoch, writer, head=_eval_loss_head(config)) \
         if evaluate and 'valid' in dataloaders else 0.0
     if rank == 0 and checkpoint:
         save_checkpoint(model=model, optimizers=optimizers, epoch=epoch, scores=[], best_ciders=(0, 0), config=config,
@@ -529,7 +562,7 @@ def train_sc(model, dataloaders, optimizers, cider, text_field, tokenizer_pool, 
             writer.add_scalar('model_lr', optimizers['model'].param_groups[0]['lr'], epoch * n + it)
     loss_fn = NLLLoss(ignore_index=_pad_index(text_field))
     _consolidate(model)
-    val_loss = evaluate_loss(model, dataloaders['valid'], loss_fn, text_field, epoch, writer) \
+    val_loss = evaluate_loss(model, dataloaders['valid'], loss_fn, text_field, epoch, writer, head=_eval_loss_head(config)) \
         if evaluate and 'valid' in dataloaders else 0.0
     if rank == 0 and checkpoint:
         save_checkpoint(model=model, optimizers=optimizers, epoch=epoch, scores=[], best_ciders=(0, 0), config=config,

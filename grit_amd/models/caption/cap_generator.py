@@ -16,13 +16,13 @@ from torch.nn import functional as F
 from grit_amd.models.caption.containers import Module, ModuleList
 from grit_amd.models.common.attention import MultiHeadAttention
 from grit_amd.models.common.pos_embed import FeedForward, sinusoid_encoding_table
-from grit_amd.ops import backend
 from grit_amd.ops import decode_inputs
 from grit_amd.ops import gate as gate_ops
 from grit_amd.ops import glue
 from grit_amd.ops import transposed as _transposed
 from grit_amd.ops import weights_epoch
 from grit_amd.ops.linear import Linear, mark_single_use, own_or_library_linear
+from grit_amd.ops.vocab_score import head_logits
 
 
 # GRIT_FUSED_STEP_INPUTS=0: masks, step counter and embedding sum of a decoding step as the reference's separate torch ops
@@ -144,7 +144,8 @@ class CaptionGenerator(Module):
         x, self.running_mask_x, mask_pad = decode_inputs.step_inputs(input, self.pad_idx, w, p, self.running_seq, self.running_mask_x)
         return x, self.running_mask_x, mask_pad
 
-    def forward(self, input, vis_inputs):
+    def hidden(self, input, vis_inputs):
+        """Everything in `forward` before the vocabulary projection: tokens (b, T) -> the last layer's states (b, T, d)."""
         if self.training and torch.is_grad_enabled() and input.is_cuda:
             _transposed.refresh_linears(self)  # W^T of every Linear: the short maps' input gradients as NT products (ops/gemm.py)
         fused = self._step_inputs(input)
@@ -154,14 +155,11 @@ class CaptionGenerator(Module):
         m1, m2 = vis_inputs['gri_mask'], vis_inputs['reg_mask']
         for layer in self.layers:
             x = layer(x, y1, y2, mask_pad, mask_x, m1, m2)
+        return x
+
+    def forward(self, input, vis_inputs):
+        x = self.hidden(input, vis_inputs)
         # vocabulary projection + log-softmax stay in float32: beam-search token identity depends on them
+        # (the projection itself is ops/vocab_score.py head_logits, shared with the composed form of the likelihood head)
         with torch.autocast(x.device.type, enabled=False):
-            w = self.fc.weight
-            if x.is_cuda and x.dtype == w.dtype == torch.bfloat16 and not torch.is_grad_enabled() and backend.override() is None:
-                # products of two bf16 values are exact in float32, so the bf16 GEMM with float32 accumulation and float32
-                # output IS the float32 projection of the same operands (summation order aside) -- without up-casting the
-                # [V, 512] weight on every step and at the bf16 matrix-core rate
-                logits = torch.mm(x.reshape(-1, x.shape[-1]), w.t(), out_dtype=torch.float32).view(*x.shape[:-1], w.shape[0])
-            else:
-                logits = F.linear(x.float(), w.float())
-            return F.log_softmax(logits, dim=-1)
+            return F.log_softmax(head_logits(x, self.fc.weight), dim=-1)

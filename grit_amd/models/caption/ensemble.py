@@ -131,6 +131,20 @@ class Ensemble(BeamSearchSteps, nn.Module):
             return self._beam_search_eager(feats, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
                                            length_penalty=length_penalty, groups=groups, force_words=force_words, **kwargs)
 
+    # ------------------------------------------------------------------ likelihood of given captions
+    def score(self, samples, captions, normalize=None):
+        """`Transformer.score` for the ensemble: every member scores `captions` on its own features, and the ensemble's
+        log-probability of a token is the mean of the members', torch.mean(torch.stack(per_member), 0) -- the rule of its beam step."""
+        captions = _tr.check_score_call(self, captions, normalize)
+        self._check_placement()
+        feats = self._member_features(samples)
+        per_member = []
+        for m, f in zip(self.models, feats):
+            with _features_mode(m):
+                per_member.append(m._score_log_probs(f, captions))
+        log_probs = torch.mean(torch.stack(per_member), 0)
+        return _tr.finish_scores(log_probs, captions, self.models[0].cap_generator.pad_idx, normalize)
+
     def _graph_eligible(self, feats, return_probs, kwargs):
         if not _tr._GRAPH_DECODE or return_probs or kwargs or self.training or torch.is_grad_enabled():
             return False

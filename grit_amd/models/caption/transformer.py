@@ -7,6 +7,7 @@ a finished beam keeps its score only at vocabulary index 0 (-999 elsewhere), sel
 the flattened [beam*V] candidates, beam = index // V, every registered state is re-gathered per step, final beams
 re-sorted by score.
 """
+import collections
 import ctypes
 import os
 from contextlib import contextmanager
@@ -19,6 +20,7 @@ from grit_amd.models.caption.base import BaseCaptioner
 from grit_amd.ops import backend
 from grit_amd.ops import beam as beam_ops
 from grit_amd.ops import sample as sample_ops
+from grit_amd.ops import vocab_score as vocab_score_ops
 from grit_amd.models.caption.cap_generator import CaptionGenerator
 from grit_amd.models.caption.grid_net import GridFeatureNetwork
 from grit_amd.utils.misc import NestedTensor
@@ -28,6 +30,36 @@ from grit_amd.utils.misc import NestedTensor
 _GRAPH_DECODE = os.environ.get('GRIT_GRAPH_DECODE', '1') != '0'
 # GRIT_FUSED_BEAM_STEP=0: the candidate / selection / gather arithmetic of a beam step as separate torch ops + grit_topk_rows_f32
 _FUSED_BEAM_STEP = os.environ.get('GRIT_FUSED_BEAM_STEP', '1') != '0'
+
+
+# What `score` returns: log_probs [B, N, T - 1] float32 (0 at pad targets), total [B, N] = their sum (divided by `length` under
+# normalize='mean'), length [B, N] int64 = the number of targets that are not pad
+CaptionScores = collections.namedtuple('CaptionScores', 'log_probs total length')
+
+
+def check_score_call(module, captions, normalize):
+    """The argument checks shared by Transformer.score and Ensemble.score -> captions as [B, N, T]."""
+    if module.training or torch.is_grad_enabled():
+        raise RuntimeError("score() measures a trained model: call model.eval() and run it under torch.no_grad() or "
+                           "torch.inference_mode() (the training loss is model(samples, captions) + NLLLoss)")
+    if normalize not in (None, 'mean'):
+        raise ValueError("normalize must be None or 'mean', not %r" % (normalize,))
+    if not isinstance(captions, torch.Tensor) or captions.dtype != torch.int64 or captions.dim() not in (2, 3):
+        raise ValueError("captions must be an int64 tensor [B, T] or [B, N, T]: <bos>, words, <eos>, then pad")
+    if captions.dim() == 2:
+        captions = captions.unsqueeze(1)
+    if captions.shape[-1] < 2 or captions.shape[1] < 1:
+        raise ValueError("captions need at least <bos> and one target per row, got shape %s" % (tuple(captions.shape),))
+    return captions
+
+
+def finish_scores(log_probs, captions, pad_idx, normalize):
+    """log_probs [B, N, T - 1] (0 at pad targets) -> CaptionScores."""
+    length = (captions[..., 1:].to(log_probs.device) != pad_idx).sum(-1)
+    total = log_probs.sum(-1)
+    if normalize == 'mean':
+        total = total / length
+    return CaptionScores(log_probs, total, length)
 
 
 class BeamSearchSteps(object):
@@ -259,6 +291,39 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
             raise ValueError("decode must be 'beam' or 'sample', not %r" % (decode,))
         return self.beam_search(images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=constraints,
                                 length_penalty=length_penalty, groups=groups, **kwargs)
+
+    # ------------------------------------------------------------------ likelihood of given captions
+    def score(self, images, captions, normalize=None):
+        """How likely the model finds `captions` for `images`: int64 [B, T] or [B, N, T] (N captions per image), each row <bos>,
+        words, <eos>, then pad.  The decoder runs teacher-forced on the B * N rows (the visual features are computed once per image
+        and repeated per caption); the target of position t is token t + 1, the last position's is pad, so the hidden map goes to
+        the likelihood head (ops/vocab_score.py) as it lies in memory.  Returns CaptionScores(log_probs [B, N, T - 1], total
+        [B, N], length [B, N]); normalize='mean' divides `total` by `length`.  Eval mode without autograd only; `images` is what
+        `forward` takes (a NestedTensor, or cached features with `cached_features` set)."""
+        captions = check_score_call(self, captions, normalize)
+        log_probs = self._score_log_probs(images, captions)
+        return finish_scores(log_probs, captions, self.cap_generator.pad_idx, normalize)
+
+    def _score_log_probs(self, images, captions):
+        """captions [B, N, T] -> log-probability of every target [B, N, T - 1] float32, 0 where the target is pad."""
+        gen = self.cap_generator
+        B, N, T = captions.shape
+        if T > gen.pos_emb.num_embeddings - 1:
+            raise ValueError("captions of %d tokens (%d targets) exceed the position table: at most %d tokens (model.max_len)"
+                             % (T, T - 1, gen.pos_emb.num_embeddings - 1))
+        batch_size, device = self.get_bs_device(images)
+        if batch_size != B:
+            raise ValueError("captions name %d images, the batch has %d" % (B, batch_size))
+        captions = captions.to(device)
+        vis = self._visual_inputs(images)
+        if N > 1:
+            vis = {k: (v.repeat_interleave(N, 0) if isinstance(v, torch.Tensor) and v.dim() > 0 and v.shape[0] == B else v)
+                   for k, v in vis.items()}
+        rows = captions.reshape(B * N, T)
+        hidden = gen.hidden(rows, vis)  # [B * N, T, D]
+        target = torch.cat([rows[:, 1:], rows.new_full((B * N, 1), gen.pad_idx)], 1)
+        logp, _ = vocab_score_ops.score(hidden.reshape(B * N * T, hidden.shape[-1]), gen.fc.weight, target.reshape(-1), gen.pad_idx)
+        return logp.view(B, N, T)[..., :-1]
 
     # ------------------------------------------------------------------ beam search
     def beam_search(self, images, max_len, eos_idx, beam_size, out_size, return_probs, constraints=None, length_penalty=0.0,

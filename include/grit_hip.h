@@ -71,7 +71,10 @@
  *   grit_jpeg_probe, grit_jpeg_entropy, grit_jpeg_reconstruct
  *                        <- PIL's Image.open(path).convert('RGB') in the dataset workers (datasets/caption/field.py:65,
  *                           tools/extract_features.py:42): libjpeg-turbo's baseline decode at its defaults
- * (none of the last eighteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
+ *   grit_vocab_score_bf16 <- CaptionGenerator.forward's `fc` + F.log_softmax (models/caption/cap_generator.py:157-167) and the gather of
+ *                           one target column per row that every caller who scores a GIVEN caption adds (the validation loss,
+ *                           engine/caption_engine.py:287-309): log-probability and log-sum-exp per row, no [rows, V] map
+ * (none of the last nineteen groups has a native ancestor in the reference: they replace chains of torch / PIL / host ops, and
  *  grit_sample_step_f32 goes one step past it)
  */
 #ifndef GRIT_HIP_H
@@ -83,7 +86,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 59
+#define GRIT_ABI_VERSION 60
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -1336,6 +1339,34 @@ int grit_jpeg_entropy(const uint8_t* data, long nbytes, const grit_jpeg_info* in
 long grit_jpeg_planes_bytes(const grit_jpeg_info* info);
 int grit_jpeg_reconstruct(const grit_jpeg_job* jobs, int n_images, int max_blocks, long max_pixels, const void* coef, uint8_t* planes,
                           uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * Caption likelihood head (DESIGN "Caption likelihood scoring"): the vocabulary projection, log-softmax and the gather of one
+ * target column per row, without the [R, V] logit map.
+ *   <- CaptionGenerator.forward's `fc` + F.log_softmax, models/caption/cap_generator.py:157-167, followed by the caller's gather.
+ *
+ * grit_vocab_score_bf16: x [R, D] bf16 (row stride ldx elements), w [V, D] bf16 (row stride ldw), target [R] int64:
+ *     logit[v] = sum_k x[r, k] w[v, k]      bf16 products, fp32 accumulation on v_mfma_f32_16x16x32_bf16
+ *     lse[r]   = log sum_v exp(logit[v])    fp32, max-subtracted
+ *     logp[r]  = logit[target[r]] - lse[r]
+ *   logp [R], lse [R] fp32.  target[r] == pad_idx: logp = +0.0 (lse is still written).  target[r] outside [0, V) and not pad_idx:
+ *   logp = NaN, nothing is read out of bounds (the host never looks at the targets).  Columns past V take no part.
+ *   Two launches, no atomics, nothing passes between the workgroups of a launch: (1) grid (ceil(R / 64), slices): a workgroup keeps
+ *   its x tile in LDS, streams its slice of w and writes the row's running (max, sum of exp) to work[slice][row]; the one lane that
+ *   holds column target[r] stores that logit; (2) one thread per row merges the pairs in slice order.  The slice width
+ *   (grit_vocab_score_slice) is a function of V and D only, so a row's bits do not depend on the other rows of the call:
+ *   f(x[idx]) == f(x)[idx], and two calls give identical bytes.
+ *   work: grit_vocab_score_workspace(R, V, D) bytes that belong to this call, 4-byte aligned, need no initialisation.
+ *   Limits (GRIT_ERR_UNSUPPORTED beyond them: the caller takes the composed form): D % 64 == 0, 64 <= D <= 512; ldx, ldw >= D and
+ *   multiples of 8; x and w 16-byte aligned; ceil(V / slice) <= 65535; R <= 2^31 - 65 (row indices are 32-bit; every offset into a
+ *   buffer is 64-bit).  Null pointers, R < 1, V < 1, D < 1: GRIT_ERR_BAD_ARG.  fp32 operands: not built.
+ * grit_vocab_score_slice: the slice width in columns (a multiple of 128), 0 for a (V, D) outside the limits.
+ * grit_vocab_score_workspace: (2 * ceil(V / slice) + 1) * R * 4 bytes, 0 outside the limits.
+ * ------------------------------------------------------------------------------------------------------ */
+int grit_vocab_score_slice(int V, int D);
+long grit_vocab_score_workspace(int R, int V, int D);
+int grit_vocab_score_bf16(const void* x, long ldx, const void* w, long ldw, const int64_t* target, long pad_idx, int R, int V, int D,
+                          void* work, float* logp, float* lse, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 
     python inference_caption.py --img image.npy|image.png [--checkpoint ckpt.pth [ckpt2.pth ...]] [--vocab data/vocab.json] [--beam 5]
                                 [--groups G --diversity X] [--n-best N] [--sample N] [--consensus --consensus-corpus captions.json]
-                                [--force "dog|dogs" frisbee]
+                                [--force "dog|dogs" frisbee] [--score "a dog catches a frisbee" ["..." ...]]
 
 Several checkpoints: one model per checkpoint, captioned together by models.caption.ensemble.Ensemble (their word
 log-probabilities averaged at every beam step).
@@ -177,6 +177,36 @@ def decode(tokens, vocab_path, eos_idx=3):
     return out
 
 
+def caption_ids(texts, stoi, bos_idx, eos_idx, pad_idx):
+    """Captions as text -> int64 [N, T]: <bos>, the ids of the lower-cased, whitespace-split words, <eos>, then pad up to the longest.
+    `stoi` maps a word to its id (a dict, or the list of words in id order); an unknown word is a ValueError that names it."""
+    if not isinstance(stoi, dict):
+        stoi = {word: i for i, word in enumerate(stoi)}
+    rows = []
+    for text in ([texts] if isinstance(texts, str) else list(texts)):
+        words = str(text).lower().split()
+        if not words:
+            raise ValueError("caption %r holds no word" % (text,))
+        for w in words:
+            if w not in stoi:
+                raise ValueError("word %r of caption %r is not in the vocabulary" % (w, text))
+        rows.append([bos_idx] + [int(stoi[w]) for w in words] + [eos_idx])
+    if not rows:
+        raise ValueError("no caption to score")
+    width = max(len(r) for r in rows)
+    return torch.tensor([r + [pad_idx] * (width - len(r)) for r in rows], dtype=torch.int64)
+
+
+@torch.inference_mode()
+def score_texts(model, image, config, ids):
+    """image [3,H,W] (already normalised), ids [N, T] (caption_ids) -> (total [N], length [N]) of the N captions for the image;
+    `model` is a Transformer or an Ensemble."""
+    device = next(model.parameters()).device
+    images = nested_tensor_from_tensor_list([image]).to(device)
+    scores = model.score(images, ids.unsqueeze(0).to(device))
+    return scores.total[0], scores.length[0]
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--img', required=True)
@@ -199,6 +229,8 @@ def build_parser():
     ap.add_argument('--top-k', type=int, default=0, help="sample among the k most probable words only (0: all)")
     ap.add_argument('--top-p', type=float, default=1.0, help="sample inside the smallest nucleus of this mass")
     ap.add_argument('--seed', type=int, default=None, help="sampling seed (default: torch's device generator)")
+    ap.add_argument('--score', nargs='+', default=[], metavar='CAPTION',
+                    help="do not caption: print how likely the model finds each given caption (log-probability, per word, text), best first")
     ap.add_argument('--consensus', action='store_true',
                     help="rerank what --n-best N or --sample N produced by consensus under CIDEr-D: the chosen caption first, then "
                          "the candidates with their consensus scores (needs --consensus-corpus)")
@@ -218,6 +250,8 @@ def parse_args(argv=None):
         ap.error("--force steers the beam search: it does not go with --sample")
     if a.force and a.groups > 1:
         ap.error("--force does not go with --groups")
+    if a.score and (a.sample > 0 or a.force or a.consensus):
+        ap.error("--score rates given captions, it decodes nothing: it does not go with --sample, --force or --consensus")
     return a
 
 
@@ -252,6 +286,8 @@ def run_main():
                                'model.beam_diversity': a.diversity, 'model.beam_force_words': list(a.force)})
     # words -> ids before anything is built: an unknown word is an error that names it
     force_words = force_words_ids(config.model.beam_force_words, vocabulary(a.vocab)) if a.force else None
+    m = config.model
+    score_ids = caption_ids(a.score, vocabulary(a.vocab), m.bos_idx, m.eos_idx, m.pad_idx) if a.score else None
     device = torch.device('cuda:0')  # the kernels need a HIP device; there is no CPU path
     model = build_captioner(config, device, a.checkpoint)
     if a.img.endswith('.npy'):
@@ -263,6 +299,12 @@ def run_main():
         rgb = np.asarray(Image.open(a.img).convert('RGB'), dtype=np.float32) / 255.0
         mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
         image = torch.from_numpy(((rgb - mean) / std).transpose(2, 0, 1))
+    if a.score:
+        total, length = score_texts(model, image, config, score_ids)
+        total, length = total.tolist(), length.tolist()
+        for i in sorted(range(len(a.score)), key=lambda i: -total[i]):  # best first
+            print('%10.4f %8.4f  %s' % (total[i], total[i] / max(length[i], 1), a.score[i]))
+        return
     if a.consensus:  # (the vocabulary is needed: consensus compares words, not ids)
         cider = consensus_cider(a.consensus_corpus)
         if a.sample > 0:
