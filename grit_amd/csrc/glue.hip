@@ -102,8 +102,11 @@ void msda_geometry_bwd(const float* __restrict__ grad_loc, const float* __restri
 // (1 - clamp(x, 0, 1)).clamp(min eps)), eps = 1e-5 (utils/misc.py inverse_sigmoid).  2-d references refine the centre only.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float inv_sigmoid(float x) {
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    return logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
+    // comparisons, not fminf / fmaxf: those return the other operand for a NaN, which turned a NaN reference point into a finite
+    // box, where torch.clamp passes it on; every other value is unchanged
+    x = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);
+    const float rest = 1.f - x;
+    return logf((x < 1e-5f ? 1e-5f : x) / (rest < 1e-5f ? 1e-5f : rest));
 }
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 

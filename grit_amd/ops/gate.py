@@ -22,12 +22,17 @@ def supported(self_att, enc1, enc2, mask_pad, fc):
             and fc.weight.shape == (d, 2 * d) and fc.bias is not None and not torch.is_autocast_enabled())
 
 
+def _rows(t, d):
+    """t as dense [rows, d] at a 16-byte aligned address (what the kernels' vector loads need): a contiguous view at an odd element
+    offset of a larger buffer is copied."""
+    t = t.reshape(-1, d).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 def pack(self_att, enc1_raw, enc2_raw, mask_pad):
     """[2R, 2d]: rows (self_att, enc1_raw * mask_pad) then rows (self_att, enc2_raw * mask_pad) -- both inputs of fc_alpha1."""
     d = self_att.shape[-1]
-    s2 = self_att.reshape(-1, d).contiguous()
-    a = enc1_raw.reshape(-1, d).contiguous()
-    b = enc2_raw.reshape(-1, d).contiguous()
+    s2, a, b = _rows(self_att, d), _rows(enc1_raw, d), _rows(enc2_raw, d)
     m = mask_pad.reshape(-1).contiguous()
     R = s2.shape[0]
     X = torch.empty((2 * R, 2 * d), dtype=s2.dtype, device=s2.device)
@@ -42,10 +47,8 @@ def fuse(enc1_raw, enc2_raw, gates, mask_pad):
     """gates [2R, d] = fc_alpha1(pack(...)) -> ((enc1 * sigmoid(gates[:R]) + enc2 * sigmoid(gates[R:])) / sqrt(2)) * mask_pad
     with enc_i = enc_i_raw * mask_pad, shaped like enc1_raw."""
     d = enc1_raw.shape[-1]
-    a = enc1_raw.reshape(-1, d).contiguous()
-    b = enc2_raw.reshape(-1, d).contiguous()
+    a, b, g = _rows(enc1_raw, d), _rows(enc2_raw, d), _rows(gates, d)
     m = mask_pad.reshape(-1).contiguous()
-    g = gates.reshape(-1, d).contiguous()
     R = a.shape[0]
     if g.shape[0] != 2 * R:
         raise _lib.GritHipError("gates must hold 2 x %d rows, got %d" % (R, g.shape[0]))
