@@ -597,231 +597,129 @@ void beam_forced_select(Src logp, long ld, Bans bans, ForcedSets f, const float*
 
 }  // namespace
 
+namespace {
+
+// Stage 1 cuts the vocabulary of every beam row into this many slices, a workgroup each.
+constexpr int beam_parts(int cur_beam) { return cur_beam == 1 ? 8 : 2; }
+
+}  // namespace
+
 extern "C" long grit_beam_step_workspace(int B, int cur_beam, int k) {
     if (B <= 0 || cur_beam <= 0 || k <= 0) return 0;
-    const int parts = cur_beam == 1 ? 8 : 2;
-    return (long)B * cur_beam * parts * kMaxK * 8;
+    return (long)B * cur_beam * beam_parts(cur_beam) * kMaxK * 8;
 }
 
 namespace {
 
-template <class Src, class Part = Src>  // Part: what stage 1 reads, Src itself or Banned<Src>
-int beam_step(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos, int first_step,
-              int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream,
-              const Bans* bans = nullptr, int groups = 0 /* 0: the plain merge */, float diversity = 0.f) {
-    if (!seq_logprob || !workspace || !sel_beam || !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob ||
-        B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V)
+// Stage 1 applies the bans when a rule is set; without one, t and history are not read.  A step with forced words always carries
+// them: its stage 2 tests the forced words against the rules.
+bool with_bans(const grit_beam_step_args& a) {
+    return a.force_words || a.no_repeat_ngram > 0 || a.no_repeat_word || a.ban_eos || a.n_suppress > 0;
+}
+
+// GRIT_OK when the step can be launched; the order of the refusals is the one that include/grit_hip.h states.
+int beam_check(const grit_beam_step_args& a) {
+    const bool bans = with_bans(a), forced = a.force_words != nullptr, grouped = a.groups > 0;
+    if (!a.maps || a.n_maps <= 0 || a.B <= 0 || a.cur_beam <= 0 || a.V <= 0 || a.k <= 0 || a.no_repeat_ngram < 0 ||
+        a.n_suppress < 0 || a.groups < 0)
         return GRIT_ERR_BAD_ARG;
-    if (!first_step && (!seq_mask || !prev_words)) return GRIT_ERR_BAD_ARG;
-    const int parts = cur_beam == 1 ? 8 : 2;
-    if (k > kMaxK || (long)k > (long)cur_beam * V || cur_beam * parts * k > 128 || (long)cur_beam * V > 0x7fffffffL || B > 65535)
+    if (bans && (a.t < 0 || (a.n_suppress > 0 && !a.suppress) || (a.t > 0 && (!a.history || a.history_ld < a.t)) ||
+                 (a.ban_eos && (a.eos < 0 || a.eos >= a.V))))
+        return GRIT_ERR_BAD_ARG;
+    if (forced && (grouped || a.n_sets < 1 || a.n_words < 1 || !a.new_met)) return GRIT_ERR_BAD_ARG;
+    // the limits of the source, the bans, the groups and the forced words
+    if (a.n_maps > kMaxMaps || (bans && (a.t > kMaxHistory || a.n_suppress > kMaxSuppress)) ||
+        ((grouped || forced) && (a.k > kMaxK || (a.cur_beam != 1 && a.cur_beam != a.k) || a.V < a.k)) ||
+        (grouped && (a.k % a.groups != 0 || !(a.diversity >= 0.f && a.diversity < INFINITY))) ||
+        (forced && (a.n_sets > kMaxSets || a.n_words > kMaxWords)))
         return GRIT_ERR_UNSUPPORTED;
-    if (workspace_bytes < grit_beam_step_workspace(B, cur_beam, k)) return GRIT_ERR_BAD_ARG;
-    Part part;
-    if constexpr (Part::kBans) {
-        if ((((V + parts - 1) / parts + 3) & ~3) > kMaxSlice) return GRIT_ERR_UNSUPPORTED;  // the ban bitmap of a slice
-        static_cast<Src&>(part) = src;
-        part.bans = *bans;
-    } else {
-        part = src;
-    }
-    float* ws_val = reinterpret_cast<float*>(workspace);
-    int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)B * cur_beam * parts * kMaxK);
-    if (k <= 5)
-        hipLaunchKernelGGL((beam_partial<5, Part>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part, ld,
-                           seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    else
-        hipLaunchKernelGGL((beam_partial<kMaxK, Part>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part, ld,
-                           seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    if (groups > 0)
-        hipLaunchKernelGGL(beam_merge_groups<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_logprob, seq_mask,
-                           prev_words, eos, first_step, cur_beam, V, k, parts, groups, diversity, ws_val, ws_idx, sel_beam, sel_word,
-                           new_seq_logprob, new_seq_mask, picked_logprob);
-    else
-        hipLaunchKernelGGL(beam_merge<Src>, dim3(B), dim3(64), 0, (hipStream_t)stream, src, ld, seq_mask, prev_words, eos,
-                           first_step, cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word, new_seq_logprob, new_seq_mask,
-                           picked_logprob);
-    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+    if (!a.seq_logprob || !a.workspace || !a.sel_beam || !a.sel_word || !a.new_seq_logprob || !a.new_seq_mask || !a.picked_logprob ||
+        a.ld < a.V || (!a.first_step && (!a.seq_mask || !a.prev_words)))
+        return GRIT_ERR_BAD_ARG;
+    for (int m = 0; m < a.n_maps; ++m)
+        if (!a.maps[m]) return GRIT_ERR_BAD_ARG;
+    for (int i = 0; bans && i < a.n_suppress; ++i)
+        if (a.suppress[i] < 0 || a.suppress[i] >= a.V) return GRIT_ERR_BAD_ARG;
+    // the limits of the plain step, and the ban bitmap of a slice
+    const int parts = beam_parts(a.cur_beam);
+    if (a.k > kMaxK || (long)a.k > (long)a.cur_beam * a.V || a.cur_beam * parts * a.k > 128 || (long)a.cur_beam * a.V > 0x7fffffffL ||
+        a.B > 65535 || (bans && (((a.V + parts - 1) / parts + 3) & ~3) > kMaxSlice))
+        return GRIT_ERR_UNSUPPORTED;
+    return a.workspace_bytes < grit_beam_step_workspace(a.B, a.cur_beam, a.k) ? GRIT_ERR_BAD_ARG : GRIT_OK;
 }
 
-}  // namespace
-
-extern "C" int grit_beam_step_f32(const float* logp, long ld, const float* seq_logprob, const float* seq_mask,
-                                  const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                                  void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-                                  float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
-    if (!logp) return GRIT_ERR_BAD_ARG;
-    return beam_step(OneMap{logp}, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
-                     workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
+Bans beam_bans(const grit_beam_step_args& a) {
+    Bans bans{};
+    bans.hist = a.history; bans.hist_ld = a.history_ld; bans.t = a.t;
+    bans.ngram = a.no_repeat_ngram; bans.repeat_word = a.no_repeat_word != 0; bans.eos_word = a.ban_eos ? a.eos : -1;
+    bans.n_sup = a.n_suppress;
+    for (int i = 0; i < a.n_suppress; ++i) bans.sup[i] = a.suppress[i];
+    return bans;
 }
 
-extern "C" int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob,
-                                       const float* seq_mask, const int64_t* prev_words, int eos, int first_step, int B,
-                                       int cur_beam, int V, int k, void* workspace, long workspace_bytes, int64_t* sel_beam,
-                                       int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
-                                       void* stream) {
-    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0) return GRIT_ERR_BAD_ARG;
-    if (n_maps > kMaxMaps) return GRIT_ERR_UNSUPPORTED;
+MeanMaps beam_mean(const grit_beam_step_args& a) {
     MeanMaps src{};
-    for (int m = 0; m < n_maps; ++m) {
-        if (!maps[m]) return GRIT_ERR_BAD_ARG;
-        src.t.p[m] = maps[m];
-    }
-    src.n = n_maps;
+    for (int m = 0; m < a.n_maps; ++m) src.t.p[m] = a.maps[m];
+    src.n = a.n_maps;
     // torch: static_cast<float>(iter.num_output_elements()) / iter.numel() -- float(N) / float(K * N), not 1 / K (they differ once
     // K * N is no longer exact in float)
-    const long outputs = (long)B * cur_beam * V;
-    src.factor = (float)outputs / (float)(outputs * n_maps);
-    return beam_step(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace, workspace_bytes,
-                     sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream);
+    const long outputs = (long)a.B * a.cur_beam * a.V;
+    src.factor = (float)outputs / (float)(outputs * a.n_maps);
+    return src;
 }
 
-namespace {
+struct Lists { int parts; float* val; int* idx; };  // what stage 1 leaves in the workspace for stage 2
 
-// The entry points with rules: the constrained step (groups == 0: the plain merge) and the diverse step.  `con`: stage 1 applies
-// the bans; without it the constraint arguments are not read.
-int beam_step_rules(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                    const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, bool con,
-                    const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos,
-                    const int* suppress, int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-                    float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream, int groups, float diversity) {
-    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0) return GRIT_ERR_BAD_ARG;
-    if (con && (t < 0 || no_repeat_ngram < 0 || n_suppress < 0 || (n_suppress > 0 && !suppress) ||
-                (t > 0 && (!history || history_ld < t)) || (ban_eos && (eos < 0 || eos >= V))))
-        return GRIT_ERR_BAD_ARG;
-    if (n_maps > kMaxMaps || (con && (t > kMaxHistory || n_suppress > kMaxSuppress))) return GRIT_ERR_UNSUPPORTED;
-    Bans bans{};
-    if (con) {
-        bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
-        bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
-        bans.n_sup = n_suppress;
-        for (int i = 0; i < n_suppress; ++i) {
-            if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
-            bans.sup[i] = suppress[i];
-        }
-    }
-    MeanMaps mean{};
-    for (int m = 0; m < n_maps; ++m) {
-        if (!maps[m]) return GRIT_ERR_BAD_ARG;
-        mean.t.p[m] = maps[m];
-    }
-    mean.n = n_maps;
-    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
-    mean.factor = (float)outputs / (float)(outputs * n_maps);
-    auto run = [&](auto src) {
-        using Src = decltype(src);
-        if (con)
-            return beam_step<Src, Banned<Src>>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
-                                               workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob,
-                                               stream, &bans, groups, diversity);
-        return beam_step<Src, Src>(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, workspace,
-                                   workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, nullptr,
-                                   groups, diversity);
-    };
-    return n_maps == 1 ? run(OneMap{maps[0]}) : run(mean);
+template <class Part>  // Part: what stage 1 reads, the source itself, Banned<Src> or Forced<Src>
+Lists beam_stage1(const Part& part, const grit_beam_step_args& a, hipStream_t stream) {
+    const int parts = beam_parts(a.cur_beam);
+    float* ws_val = reinterpret_cast<float*>(a.workspace);
+    int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)a.B * a.cur_beam * parts * kMaxK);
+    const auto kernel = a.k <= 5 ? beam_partial<5, Part> : beam_partial<kMaxK, Part>;
+    hipLaunchKernelGGL(kernel, dim3(parts, a.cur_beam, a.B), dim3(kBeamThreads), 0, stream, part, a.ld, a.seq_logprob, a.seq_mask,
+                       a.prev_words, a.eos, a.first_step, a.cur_beam, a.V, a.k, parts, ws_val, ws_idx);
+    return {parts, ws_val, ws_idx};
 }
 
-}  // namespace
-
-extern "C" int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                                      const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                                      const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
-                                      int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
-                                      int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
-                                      float* picked_logprob, void* stream) {
-    return beam_step_rules(maps, n_maps, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, true, history,
-                           history_ld, t, no_repeat_ngram, no_repeat_word, ban_eos, suppress, n_suppress, workspace, workspace_bytes,
-                           sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, 0, 0.f);
-}
-
-extern "C" int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                                      const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                                      int groups, float diversity, const int64_t* history, long history_ld, int t,
-                                      int no_repeat_ngram, int no_repeat_word, int ban_eos, const int* suppress, int n_suppress,
-                                      void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-                                      float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream) {
-    if (k <= 0 || groups < 1 || no_repeat_ngram < 0 || n_suppress < 0) return GRIT_ERR_BAD_ARG;
-    if (k > kMaxK || k % groups != 0 || (cur_beam != 1 && cur_beam != k) || V < k || !(diversity >= 0.f && diversity < INFINITY))
-        return GRIT_ERR_UNSUPPORTED;
-    const bool con = no_repeat_ngram > 0 || no_repeat_word || ban_eos || n_suppress > 0;  // all off: t and history are not read
-    return beam_step_rules(maps, n_maps, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, con, history,
-                           history_ld, t, no_repeat_ngram, no_repeat_word, ban_eos, suppress, n_suppress, workspace, workspace_bytes,
-                           sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, stream, groups, diversity);
-}
-
-namespace {
-
-template <class Src>
-int beam_step_forced(Src src, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words, int eos,
-                     int first_step, int B, int cur_beam, int V, int k, const Bans& bans, const ForcedSets& sets, void* workspace,
-                     long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
-                     float* picked_logprob, int* new_met, void* stream) {
-    const int parts = cur_beam == 1 ? 8 : 2;
-    if ((long)cur_beam * V > 0x7fffffffL || B > 65535 || cur_beam * parts * k > 128 ||
-        (((V + parts - 1) / parts + 3) & ~3) > kMaxSlice)
-        return GRIT_ERR_UNSUPPORTED;
-    if (workspace_bytes < grit_beam_step_workspace(B, cur_beam, k)) return GRIT_ERR_BAD_ARG;
-    Forced<Src> part;
+// The two launches of a step whose stage 1 reads Part = Src (plain), Banned<Src> or Forced<Src>; stage 2 reads the plain source.
+template <class Part, class Src>
+int beam_step(const Src& src, const grit_beam_step_args& a, hipStream_t stream) {
+    Part part;
     static_cast<Src&>(part) = src;
-    part.bans = bans;
-    part.forced = sets;
-    float* ws_val = reinterpret_cast<float*>(workspace);
-    int* ws_idx = reinterpret_cast<int*>(ws_val + (size_t)B * cur_beam * parts * kMaxK);
-    if (k <= 5)
-        hipLaunchKernelGGL((beam_partial<5, Forced<Src>>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream, part,
-                           ld, seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
+    if constexpr (Part::kBans) part.bans = beam_bans(a);
+    if constexpr (Part::kForced) part.forced = ForcedSets{a.force_words, a.met_in, a.n_sets, a.n_words};
+    const Lists l = beam_stage1(part, a, stream);
+    if constexpr (Part::kForced)
+        hipLaunchKernelGGL(beam_forced_select<Src>, dim3(a.B), dim3(kBeamThreads), 0, stream, src, a.ld, part.bans, part.forced,
+                           a.seq_logprob, a.seq_mask, a.prev_words, a.eos, a.first_step, a.cur_beam, a.V, a.k, l.parts, l.val, l.idx,
+                           a.sel_beam, a.sel_word, a.new_seq_logprob, a.new_seq_mask, a.picked_logprob, a.new_met);
+    else if (a.groups > 0)
+        hipLaunchKernelGGL(beam_merge_groups<Src>, dim3(a.B), dim3(64), 0, stream, src, a.ld, a.seq_logprob, a.seq_mask, a.prev_words,
+                           a.eos, a.first_step, a.cur_beam, a.V, a.k, l.parts, a.groups, a.diversity, l.val, l.idx, a.sel_beam, a.sel_word,
+                           a.new_seq_logprob, a.new_seq_mask, a.picked_logprob);
     else
-        hipLaunchKernelGGL((beam_partial<kMaxK, Forced<Src>>), dim3(parts, cur_beam, B), dim3(kBeamThreads), 0, (hipStream_t)stream,
-                           part, ld, seq_logprob, seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx);
-    hipLaunchKernelGGL(beam_forced_select<Src>, dim3(B), dim3(kBeamThreads), 0, (hipStream_t)stream, src, ld, bans, sets, seq_logprob,
-                       seq_mask, prev_words, eos, first_step, cur_beam, V, k, parts, ws_val, ws_idx, sel_beam, sel_word,
-                       new_seq_logprob, new_seq_mask, picked_logprob, new_met);
+        hipLaunchKernelGGL(beam_merge<Src>, dim3(a.B), dim3(64), 0, stream, src, a.ld, a.seq_mask, a.prev_words, a.eos, a.first_step,
+                           a.cur_beam, a.V, a.k, l.parts, l.val, l.idx, a.sel_beam, a.sel_word, a.new_seq_logprob, a.new_seq_mask,
+                           a.picked_logprob);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }
 
 }  // namespace
 
-extern "C" int grit_beam_step_forced_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                                         const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                                         const int64_t* force_words, int n_sets, int n_words, const int* met_in,
-                                         const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
-                                         int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
-                                         int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
-                                         float* picked_logprob, int* new_met, void* stream) {
-    if (!maps || n_maps <= 0 || B <= 0 || cur_beam <= 0 || V <= 0 || k <= 0 || ld < V || !seq_logprob || !workspace || !sel_beam ||
-        !sel_word || !new_seq_logprob || !new_seq_mask || !picked_logprob || !new_met || !force_words || n_sets < 1 || n_words < 1)
-        return GRIT_ERR_BAD_ARG;
-    if (!first_step && (!seq_mask || !prev_words)) return GRIT_ERR_BAD_ARG;
-    if (t < 0 || no_repeat_ngram < 0 || n_suppress < 0 || (n_suppress > 0 && !suppress) || (t > 0 && (!history || history_ld < t)) ||
-        (ban_eos && (eos < 0 || eos >= V)))
-        return GRIT_ERR_BAD_ARG;
-    if (n_maps > kMaxMaps || k > kMaxK || (cur_beam != 1 && cur_beam != k) || V < k || n_sets > kMaxSets || n_words > kMaxWords ||
-        t > kMaxHistory || n_suppress > kMaxSuppress)
-        return GRIT_ERR_UNSUPPORTED;
-    Bans bans{};
-    bans.hist = history; bans.hist_ld = history_ld; bans.t = t;
-    bans.ngram = no_repeat_ngram; bans.repeat_word = no_repeat_word != 0; bans.eos_word = ban_eos ? eos : -1;
-    bans.n_sup = n_suppress;
-    for (int i = 0; i < n_suppress; ++i) {
-        if (suppress[i] < 0 || suppress[i] >= V) return GRIT_ERR_BAD_ARG;
-        bans.sup[i] = suppress[i];
-    }
-    const ForcedSets sets{force_words, met_in, n_sets, n_words};
-    MeanMaps mean{};
-    for (int m = 0; m < n_maps; ++m) {
-        if (!maps[m]) return GRIT_ERR_BAD_ARG;
-        mean.t.p[m] = maps[m];
-    }
-    mean.n = n_maps;
-    const long outputs = (long)B * cur_beam * V;  // as in grit_beam_step_mean_f32
-    mean.factor = (float)outputs / (float)(outputs * n_maps);
-    auto run = [&](auto src) {
-        return beam_step_forced(src, ld, seq_logprob, seq_mask, prev_words, eos, first_step, B, cur_beam, V, k, bans, sets, workspace,
-                                workspace_bytes, sel_beam, sel_word, new_seq_logprob, new_seq_mask, picked_logprob, new_met, stream);
-    };
-    return n_maps == 1 ? run(OneMap{maps[0]}) : run(mean);
+extern "C" int grit_beam_step(const grit_beam_step_args* args, void* stream) {
+    if (!args) return GRIT_ERR_BAD_ARG;
+    const grit_beam_step_args& a = *args;
+    const int status = beam_check(a);
+    if (status != GRIT_OK) return status;
+    hipStream_t s = (hipStream_t)stream;
+    const bool one = a.n_maps == 1;
+    const OneMap map{a.maps[0]};
+    const MeanMaps mean = beam_mean(a);
+    if (!with_bans(a)) return one ? beam_step<OneMap>(map, a, s) : beam_step<MeanMaps>(mean, a, s);
+    if (!a.force_words) return one ? beam_step<Banned<OneMap>>(map, a, s) : beam_step<Banned<MeanMaps>>(mean, a, s);
+    return one ? beam_step<Forced<OneMap>>(map, a, s) : beam_step<Forced<MeanMaps>>(mean, a, s);
 }
+
 
 extern "C" int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t* idx_out, float* val_out, void* stream) {
     if (!x || !idx_out || !val_out || rows <= 0 || n <= 0 || k <= 0) return GRIT_ERR_BAD_ARG;

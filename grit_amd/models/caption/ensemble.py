@@ -4,7 +4,7 @@ Every step each member produces its word log-probabilities from its own visual f
 ensemble's word log-probability is their mean, torch.mean(torch.stack(per_model), 0) (reference :128-162), and the rest of
 the step -- finished-beam masking, candidate scores, selection, the score / mask / log-prob gathers, every member's states
 re-gathered by the surviving beams -- is `Transformer.iter`'s (reference :164-214).  On a HIP device the mean and the step are
-one fused pair of launches (grit_beam_step_mean_f32: the averaged map is never written) and the whole K-model decode from
+one fused pair of launches (grit_beam_step with n_maps = K: the averaged map is never written) and the whole K-model decode from
 features is captured once per shape into a HIP graph and replayed, with the policy of `Transformer._beam_search_graphed`.
 
 The reference class reads `model.encoder`, `model.decoder`, `det_feat` and `config.model.decoder.decoder_name`, names left
@@ -234,22 +234,11 @@ class Ensemble(BeamSearchSteps, nn.Module):
         fused, word_logprob = None, None
         if constraints is not None:
             outputs = self._history(outputs)
-        on_device = beam_ops.supported_mean(maps, cur_beam, beam_size) if groups is None else \
-            beam_ops.supported_div(maps, cur_beam, beam_size, groups.num_groups)
-        if force_words is not None:
-            on_device = beam_ops.supported_forced(maps, cur_beam, beam_size)
-        if _tr._FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
+        if _tr._FUSED_BEAM_STEP and not return_probs and not kwargs:  # None where the step stays off the kernel: the composed form
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if force_words is not None:  # None beyond the kernel's limits, here and below: the composed form
-                fused = beam_ops.beam_step_forced(maps, *state, force_words, self.met if timestep > 0 else None,
-                                                  outputs[0] if outputs else None, timestep, constraints)
-            elif groups is not None:
-                fused = beam_ops.beam_step_div(maps, *state, *groups, outputs[0] if outputs else None, timestep, constraints)
-            elif constraints is None:
-                fused = beam_ops.beam_step_mean(maps, *state)
-            else:
-                fused = beam_ops.beam_step_con(maps, *state, outputs[0] if outputs else None, timestep, constraints)
+            met = self.met if force_words is not None and timestep > 0 else None
+            fused = beam_ops.fused_step(maps, state, constraints, groups, force_words, met, outputs[0] if outputs else None, timestep)
         if fused is None:
             word_logprob = torch.mean(torch.stack(maps), 0)
         outputs = self._beam_advance(self.models, timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,

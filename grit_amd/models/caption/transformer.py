@@ -534,23 +534,14 @@ class Transformer(BeamSearchSteps, BaseCaptioner):
         fused = None
         if constraints is not None:
             outputs = self._history(outputs)
-        on_device = beam_ops.supported(word_logprob, cur_beam, beam_size) if groups is None else \
-            beam_ops.supported_div([word_logprob], cur_beam, beam_size, groups.num_groups)
-        if force_words is not None:
-            on_device = beam_ops.supported_forced([word_logprob], cur_beam, beam_size)
-        if _FUSED_BEAM_STEP and not return_probs and not kwargs and on_device:
-            # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py)
+        if _FUSED_BEAM_STEP and not return_probs and not kwargs:
+            # masking, candidate scores, selection and the score / mask / log-prob gathers in two launches (ops/beam.py); None
+            # where the step stays off the kernel: the composed form
             state = (self.seq_logprob, self.seq_mask if timestep > 0 else None, self.selected_words if timestep > 0 else None,
                      eos_idx, beam_size)
-            if force_words is not None:  # None beyond the kernel's limits, here and below: the composed form
-                fused = beam_ops.beam_step_forced([word_logprob], *state, force_words, self.met if timestep > 0 else None,
-                                                  outputs[0] if outputs else None, timestep, constraints)
-            elif groups is not None:
-                fused = beam_ops.beam_step_div([word_logprob], *state, *groups, outputs[0] if outputs else None, timestep, constraints)
-            elif constraints is None:
-                fused = beam_ops.beam_step(word_logprob, *state)
-            else:
-                fused = beam_ops.beam_step_con([word_logprob], *state, outputs[0] if outputs else None, timestep, constraints)
+            met = self.met if force_words is not None and timestep > 0 else None
+            fused = beam_ops.fused_step([word_logprob], state, constraints, groups, force_words, met, outputs[0] if outputs else None,
+                                        timestep)
         outputs = self._beam_advance((self,), timestep, word_logprob, fused, outputs, return_probs, batch_size, beam_size,
                                      eos_idx, constraints=constraints, groups=groups, force_words=force_words, **kwargs)
         return samples, outputs

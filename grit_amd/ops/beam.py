@@ -1,10 +1,10 @@
-"""One beam-search step after the decoder as two launches (grit_beam_step_f32, include/grit_hip.h): the finished-beam masking,
+"""One beam-search step after the decoder as two launches (grit_beam_step, include/grit_hip.h): the finished-beam masking,
 candidate scores, top-k over beam x vocabulary, beam / word split and the score / mask / log-prob gathers of the reference's
 Transformer.iter (models/caption/transformer.py:208-240), bit-identical to the composed torch form.  `beam_step_mean` is the same
-step for an ensemble (models/caption/ensemble.py:128-214): the average of the members' maps (grit_beam_step_mean_f32).  Past the
-reference: the step under constraints (grit_beam_step_con_f32), the step of a diverse search over beam groups
-(grit_beam_step_div_f32) and the step of a search with forced words (grit_beam_step_forced_f32), each with its host form in
-torch ops."""
+step for an ensemble (models/caption/ensemble.py:128-214): the average of the members' maps.  Past the reference: the step under
+constraints (`beam_step_con`), the step of a diverse search over beam groups (`beam_step_div`) and the step of a search with forced
+words (`beam_step_forced`), each with its host form in torch ops.  All five are fronts over `_step`, the one place that fills
+grit_beam_step_args and launches; `fused_step` chooses among them for the decoders."""
 import collections
 import ctypes
 
@@ -14,48 +14,13 @@ from grit_amd import lib as _lib
 from grit_amd.ops import backend
 
 
-_ptr = _lib.ptr
-
-
 def supported(word_logprob, cur_beam, beam_size):
     return (word_logprob.is_cuda and word_logprob.dtype == torch.float32 and not word_logprob.requires_grad
             and not torch.is_grad_enabled() and backend.override() is None and beam_size <= 8
             and cur_beam * beam_size * (8 if cur_beam == 1 else 2) <= 128 and word_logprob.shape[0] <= 65535)
 
 
-def beam_step(word_logprob, seq_logprob, seq_mask, prev_words, eos_idx, beam_size):
-    """word_logprob [B, cur_beam, V] f32, seq_logprob [B, cur_beam, 1], seq_mask [B, cur_beam, 1] and prev_words [B * cur_beam, 1]
-    (both None at the first step) -> sel_beam, sel_word [B, beam] int64, seq_logprob, seq_mask, picked log-prob [B, beam, 1] f32."""
-    B, cur, V = word_logprob.shape
-    lp = word_logprob if word_logprob.is_contiguous() else word_logprob.contiguous()
-    first = prev_words is None
-    dev = lp.device
-    L = _lib.load()
-    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    slp = seq_logprob.reshape(-1).float().contiguous()
-    if slp.numel() != B * cur:
-        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
-    sm = pw = None
-    if not first:
-        sm = seq_mask.reshape(-1).float().contiguous()
-        pw = prev_words.reshape(-1).contiguous()
-        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
-            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
-    with _lib.device_guard(dev):
-        st = L.grit_beam_step_f32(_ptr(lp), lp.stride(1), _ptr(slp), _ptr(sm), _ptr(pw), int(eos_idx), int(first), B, cur, V,
-                                  beam_size, _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp), _ptr(new_mask),
-                                  _ptr(picked), _lib.current_stream_ptr())
-    _lib.check(st, "grit_beam_step_f32")
-    return sel_beam, sel_word, new_lp, new_mask, picked
-
-
-MAX_MAPS = 8  # grit_beam_step_mean_f32
+MAX_MAPS = 8  # grit_beam_step: n_maps
 
 
 def supported_mean(word_logprobs, cur_beam, beam_size):
@@ -66,14 +31,45 @@ def supported_mean(word_logprobs, cur_beam, beam_size):
                     for m in word_logprobs))
 
 
-def beam_step_mean(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size):
-    """`beam_step` on the average of K <= 8 word log-probability maps ([B, cur_beam, V] f32 each, one per ensemble member), as
-    torch.stack(word_logprobs).mean(0) computes it on the device, bit for bit (grit_beam_step_mean_f32).  The average is formed
-    inside the kernel and never written; the returned picked log-prob is the averaged value."""
-    B, cur, V = word_logprobs[0].shape
-    maps = [m if m.is_contiguous() else m.contiguous() for m in word_logprobs]
+def _address(tensor):
+    return None if tensor is None else tensor.data_ptr()
+
+
+def _step(maps, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, con=None, history=None, t=0, groups=None, force_words=None,
+          met=None, or_none=True):
+    """grit_beam_step on one map or on the mean of several: the arguments of `beam_step`, and optionally the constraint tuple `con`
+    with history [B, cur_beam, t] int64 (None at t == 0) and the step `t`, the `groups` tuple (num_groups, diversity), and
+    force_words [B, C, W] int64 with met [B, cur_beam] int32 (None: the first step).  Returns the five outputs of `beam_step`, and
+    new_met [B, beam] int32 behind them for forced words.  Outside the kernel's limits nothing is launched: None when `or_none`
+    (the caller uses the host form), else GritHipError."""
+    B, cur, V = maps[0].shape
+    # the limits that the rules add, before the library is touched
+    if con is not None and (t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS):
+        return None
+    if (groups is not None or force_words is not None) and \
+            (beam_size > 8 or V < beam_size or cur not in (1, beam_size) or len(maps) > MAX_MAPS):
+        return None
+    if groups is not None and beam_size % groups.num_groups != 0:
+        return None
+    if force_words is not None and not (1 <= force_words.shape[1] <= MAX_FORCED_SETS
+                                        and 1 <= force_words.shape[2] <= MAX_FORCED_WORDS):
+        return None
+    # the kernel reads evenly spaced rows of adjacent words (any row stride >= V); every other layout is copied
+    ld = {m.stride(0) if cur == 1 else m.stride(1) for m in maps}
+    spaced = len(ld) == 1 and min(ld) >= V and all(m.stride(2) == 1 and (cur == 1 or m.stride(0) == cur * m.stride(1))
+                                                   for m in maps)
+    maps = list(maps) if spaced else [m.contiguous() for m in maps]
+    ld = min(ld) if spaced else V
     first = prev_words is None
     dev = maps[0].device
+    if force_words is not None:
+        if force_words.shape[0] != B or force_words.dtype != torch.int64 or force_words.device != dev:
+            raise _lib.GritHipError("force_words must be int64 [%d, sets, words] on %s" % (B, dev))
+        force_words = force_words if force_words.is_contiguous() else force_words.contiguous()
+        if met is not None:
+            if met.numel() != B * cur or met.dtype != torch.int32 or met.device != dev:
+                raise _lib.GritHipError("met must be int32 with %d x %d entries on %s" % (B, cur, dev))
+            met = met.reshape(-1).contiguous()
     L = _lib.load()
     nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -92,13 +88,50 @@ def beam_step_mean(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, be
         if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
             raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
     table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host array: passed by value to the kernel
+    args = _lib.BeamStepArgs(
+        maps=ctypes.addressof(table), n_maps=len(maps), ld=ld, seq_logprob=slp.data_ptr(), seq_mask=_address(sm),
+        prev_words=_address(pw), eos=int(eos_idx), first_step=int(first), B=B, cur_beam=cur, V=V, k=beam_size,
+        workspace=ws.data_ptr(), workspace_bytes=nbytes, sel_beam=sel_beam.data_ptr(), sel_word=sel_word.data_ptr(),
+        new_seq_logprob=new_lp.data_ptr(), new_seq_mask=new_mask.data_ptr(), picked_logprob=picked.data_ptr())
+    outputs = (sel_beam, sel_word, new_lp, new_mask, picked)
+    if con is not None:
+        hist = None
+        if t > 0:
+            hist = history.reshape(B * cur, -1)
+            if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
+                raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
+            hist = hist if hist.stride(1) == 1 else hist.contiguous()
+            args.history, args.history_ld = hist.data_ptr(), hist.stride(0)
+        ids = (ctypes.c_int * len(con.suppress))(*con.suppress)  # host array as well
+        args.t, args.no_repeat_ngram, args.no_repeat_word = int(t), con.no_repeat_ngram, int(con.no_repeat_word)
+        args.ban_eos, args.suppress, args.n_suppress = int(t < con.min_len), ctypes.addressof(ids), len(ids)
+    if groups is not None:
+        args.groups, args.diversity = int(groups.num_groups), float(groups.diversity)
+    if force_words is not None:
+        new_met = torch.empty((B, beam_size), dtype=torch.int32, device=dev)
+        args.force_words, args.n_sets, args.n_words = force_words.data_ptr(), force_words.shape[1], force_words.shape[2]
+        args.met_in, args.new_met = _address(met), new_met.data_ptr()
+        outputs += (new_met,)
     with _lib.device_guard(dev):
-        st = L.grit_beam_step_mean_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), maps[0].stride(1), _ptr(slp), _ptr(sm),
-                                       _ptr(pw), int(eos_idx), int(first), B, cur, V, beam_size, _ptr(ws), nbytes,
-                                       _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp), _ptr(new_mask), _ptr(picked),
-                                       _lib.current_stream_ptr())
-    _lib.check(st, "grit_beam_step_mean_f32")
-    return sel_beam, sel_word, new_lp, new_mask, picked
+        st = L.grit_beam_step(ctypes.byref(args), _lib.current_stream_ptr())
+    if st == _lib.ERR_UNSUPPORTED and or_none:
+        return None
+    _lib.check(st, "grit_beam_step")
+    return outputs
+
+
+def beam_step(word_logprob, seq_logprob, seq_mask, prev_words, eos_idx, beam_size):
+    """word_logprob [B, cur_beam, V] f32, seq_logprob [B, cur_beam, 1], seq_mask [B, cur_beam, 1] and prev_words [B * cur_beam, 1]
+    (both None at the first step) -> sel_beam, sel_word [B, beam] int64, seq_logprob, seq_mask, picked log-prob [B, beam, 1] f32."""
+    return _step([word_logprob], seq_logprob, seq_mask, prev_words, eos_idx, beam_size, or_none=False)
+
+
+def beam_step_mean(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size):
+    """`beam_step` on the average of K <= 8 word log-probability maps ([B, cur_beam, V] f32 each, one per ensemble member), as
+    torch.stack(word_logprobs).mean(0) computes it on the device, bit for bit.  The average is formed inside the kernel and never
+    written; the returned picked log-prob is the averaged value."""
+    return _step(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, or_none=False)
+
 
 
 # ------------------------------------------------------------------------------------------------------ constraints
@@ -106,8 +139,8 @@ def beam_step_mean(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, be
 #   <eos> while t < min_len; any id of `suppress`; h_{t-1} under no_repeat_word; and, for no_repeat_ngram = n >= 1, the word
 #   h_{i+n-1} of every 0 <= i <= t - n with h_i .. h_{i+n-2} == h_{t-n+1} .. h_{t-1} (n = 1: every word used so far).
 # A finished beam has no bans: it lives through vocabulary index 0 alone.  A banned candidate scores -inf and stays a candidate.
-# `banned_words_host` states this in torch ops (CPU, wide beams, beam search with gradient); grit_beam_step_con_f32 is the same
-# on the device inside the two launches of the step.
+# `banned_words_host` states this in torch ops (CPU, wide beams, beam search with gradient); grit_beam_step with its bans is the
+# same on the device inside the two launches of the step.
 Constraints = collections.namedtuple("Constraints", "min_len no_repeat_ngram no_repeat_word suppress")
 MAX_HISTORY, MAX_SUPPRESS, MAX_SLICE = _lib.BEAM_MAX_HISTORY, _lib.BEAM_MAX_SUPPRESS, _lib.BEAM_MAX_SLICE
 
@@ -167,49 +200,9 @@ def banned_words_host(history, alive, t, eos, V, min_len=0, suppress=(), no_repe
 
 def beam_step_con(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, history, t, con):
     """`beam_step` (one map) or `beam_step_mean` (several) under the constraint tuple `con` at step `t`, history [B, cur_beam, t]
-    int64 (None at t == 0): grit_beam_step_con_f32, two launches, nothing uploaded.  Returns None when the call is outside the
-    kernel's limits (t > 64, more than 16 suppress ids, a vocabulary slice above 65536 words): the caller uses the host form."""
-    if t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS:
-        return None
-    B, cur, V = word_logprobs[0].shape
-    maps = [m if m.is_contiguous() else m.contiguous() for m in word_logprobs]
-    first = prev_words is None
-    dev = maps[0].device
-    L = _lib.load()
-    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    slp = seq_logprob.reshape(-1).float().contiguous()
-    if slp.numel() != B * cur:
-        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
-    sm = pw = hist = None
-    if not first:
-        sm = seq_mask.reshape(-1).float().contiguous()
-        pw = prev_words.reshape(-1).contiguous()
-        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
-            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
-    if t > 0:
-        hist = history.reshape(B * cur, -1)
-        if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
-            raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
-        hist = hist if hist.stride(1) == 1 else hist.contiguous()
-    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host arrays: passed by value to the kernel
-    ids = (ctypes.c_int * max(1, len(con.suppress)))(*con.suppress)
-    with _lib.device_guard(dev):
-        st = L.grit_beam_step_con_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), maps[0].stride(1), _ptr(slp), _ptr(sm),
-                                      _ptr(pw), int(eos_idx), int(first), B, cur, V, beam_size, _ptr(hist),
-                                      hist.stride(0) if hist is not None else 0, int(t), con.no_repeat_ngram,
-                                      int(con.no_repeat_word), int(t < con.min_len), ctypes.cast(ids, ctypes.c_void_p),
-                                      len(con.suppress), _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp),
-                                      _ptr(new_mask), _ptr(picked), _lib.current_stream_ptr())
-    if st == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(st, "grit_beam_step_con_f32")
-    return sel_beam, sel_word, new_lp, new_mask, picked
+    int64 (None at t == 0): two launches, nothing uploaded.  Returns None when the call is outside the kernel's limits (t > 64,
+    more than 16 suppress ids, a vocabulary slice above 65536 words): the caller uses the host form."""
+    return _step(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, con, history, t)
 
 
 # ------------------------------------------------------------------------------------------------------ beam groups
@@ -223,7 +216,7 @@ def beam_step_con(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, bea
 # and takes its g best of its g * V candidates, value descending, ties by ascending row * V + word.  At the first step every group
 # reads row 0.  The running score that moves on is the PENALISED value (as the generation libraries keep it), `picked` the
 # unpenalised word log-prob.  With counts == 0 the score is the plain step's bit for bit.  `beam_step_groups_host` states this in
-# torch ops; grit_beam_step_div_f32 is the same on the device in the two launches of a step.
+# torch ops; grit_beam_step with groups >= 1 is the same on the device in the two launches of a step.
 Groups = collections.namedtuple("Groups", "num_groups diversity")
 
 
@@ -298,60 +291,12 @@ def supported_div(word_logprobs, cur_beam, beam_size, num_groups):
 
 def beam_step_div(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, num_groups, diversity, history=None, t=0,
                   con=None):
-    """The grouped step of one map or of the mean of several on the device (grit_beam_step_div_f32: two launches, nothing
-    uploaded), under the constraint tuple `con` (None: unconstrained; history and t are then not read).  Returns None when the call
-    is outside the kernel's limits (a beam above 8, fewer words than beams, and with constraints t > 64 or more than 16 suppress
-    ids or a slice above 65536 words): the caller uses `beam_step_groups_host`."""
-    B, cur, V = word_logprobs[0].shape
-    if beam_size > 8 or V < beam_size or cur not in (1, beam_size) or beam_size % num_groups != 0 or len(word_logprobs) > MAX_MAPS:
-        return None
-    if con is not None and (t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS):
-        return None
-    # the kernel reads evenly spaced rows of adjacent words (any row stride >= V); every other layout is copied
-    ld = {m.stride(0) if cur == 1 else m.stride(1) for m in word_logprobs}
-    spaced = len(ld) == 1 and min(ld) >= V and all(m.stride(2) == 1 and (cur == 1 or m.stride(0) == cur * m.stride(1))
-                                                   for m in word_logprobs)
-    maps = list(word_logprobs) if spaced else [m.contiguous() for m in word_logprobs]
-    ld = min(ld) if spaced else V
-    first = prev_words is None
-    dev = maps[0].device
-    L = _lib.load()
-    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    slp = seq_logprob.reshape(-1).float().contiguous()
-    if slp.numel() != B * cur:
-        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
-    sm = pw = hist = None
-    if not first:
-        sm = seq_mask.reshape(-1).float().contiguous()
-        pw = prev_words.reshape(-1).contiguous()
-        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
-            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
-    if con is None:
-        con, t = Constraints(0, 0, False, ()), 0
-    if t > 0:
-        hist = history.reshape(B * cur, -1)
-        if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
-            raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
-        hist = hist if hist.stride(1) == 1 else hist.contiguous()
-    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host arrays: passed by value to the kernel
-    ids = (ctypes.c_int * max(1, len(con.suppress)))(*con.suppress)
-    with _lib.device_guard(dev):
-        st = L.grit_beam_step_div_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), ld, _ptr(slp), _ptr(sm),
-                                      _ptr(pw), int(eos_idx), int(first), B, cur, V, beam_size, int(num_groups), float(diversity),
-                                      _ptr(hist), hist.stride(0) if hist is not None else 0, int(t), con.no_repeat_ngram,
-                                      int(con.no_repeat_word), int(t < con.min_len), ctypes.cast(ids, ctypes.c_void_p),
-                                      len(con.suppress), _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp),
-                                      _ptr(new_mask), _ptr(picked), _lib.current_stream_ptr())
-    if st == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(st, "grit_beam_step_div_f32")
-    return sel_beam, sel_word, new_lp, new_mask, picked
+    """The grouped step of one map or of the mean of several on the device (two launches, nothing uploaded), under the constraint
+    tuple `con` (None: unconstrained; history and t are then not read).  Returns None when the call is outside the kernel's limits
+    (a beam above 8, fewer words than beams, and with constraints t > 64 or more than 16 suppress ids or a slice above 65536
+    words): the caller uses `beam_step_groups_host`."""
+    return _step(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, con, history, t,
+                 groups=Groups(num_groups, diversity))
 
 
 # ------------------------------------------------------------------------------------------------------ forced words
@@ -371,7 +316,7 @@ def beam_step_div(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, bea
 #      until k are chosen;
 #   7. outputs in the order of choice: sel_beam, sel_word, the candidate's score, the source row's liveness, the stored log-prob
 #      times liveness, and new_met = met'.
-# `beam_step_forced_host` states this in torch ops; grit_beam_step_forced_f32 is the same on the device in two launches.
+# `beam_step_forced_host` states this in torch ops; grit_beam_step with force_words is the same on the device in two launches.
 MAX_FORCED_SETS, MAX_FORCED_WORDS = _lib.BEAM_MAX_FORCED_SETS, _lib.BEAM_MAX_FORCED_WORDS
 
 
@@ -499,69 +444,29 @@ def supported_forced(word_logprobs, cur_beam, beam_size):
 
 def beam_step_forced(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, force_words, met=None, history=None, t=0,
                      con=None):
-    """The step with forced words of one map or of the mean of several on the device (grit_beam_step_forced_f32: two launches,
-    nothing uploaded): force_words [B, C, W] int64 and met [B, cur_beam] int32 (None: the first step) are device tensors.  Returns
-    the five outputs of `beam_step` and new_met [B, beam] int32, or None when the call is outside the kernel's limits (a beam above
-    8, fewer words than beams, more than 8 sets or 4 words a set, and the limits of `beam_step_con`): the caller uses
-    `beam_step_forced_host`."""
-    B, cur, V = word_logprobs[0].shape
-    C, W = force_words.shape[1], force_words.shape[2]
-    if beam_size > 8 or V < beam_size or cur not in (1, beam_size) or len(word_logprobs) > MAX_MAPS:
-        return None
-    if not (1 <= C <= MAX_FORCED_SETS and 1 <= W <= MAX_FORCED_WORDS):
-        return None
-    if con is not None and (t > MAX_HISTORY or len(con.suppress) > MAX_SUPPRESS):
-        return None
-    # the kernel reads evenly spaced rows of adjacent words (any row stride >= V); every other layout is copied
-    ld = {m.stride(0) if cur == 1 else m.stride(1) for m in word_logprobs}
-    spaced = len(ld) == 1 and min(ld) >= V and all(m.stride(2) == 1 and (cur == 1 or m.stride(0) == cur * m.stride(1))
-                                                   for m in word_logprobs)
-    maps = list(word_logprobs) if spaced else [m.contiguous() for m in word_logprobs]
-    ld = min(ld) if spaced else V
-    first = prev_words is None
-    dev = maps[0].device
-    if force_words.shape[0] != B or force_words.dtype != torch.int64 or force_words.device != dev:
-        raise _lib.GritHipError("force_words must be int64 [%d, sets, words] on %s" % (B, dev))
-    fw = force_words if force_words.is_contiguous() else force_words.contiguous()
-    if met is not None:
-        if met.numel() != B * cur or met.dtype != torch.int32 or met.device != dev:
-            raise _lib.GritHipError("met must be int32 with %d x %d entries on %s" % (B, cur, dev))
-        met = met.reshape(-1).contiguous()
-    L = _lib.load()
-    nbytes = L.grit_beam_step_workspace(B, cur, beam_size)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    sel_beam = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    sel_word = torch.empty((B, beam_size), dtype=torch.int64, device=dev)
-    new_lp = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    new_mask = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    picked = torch.empty((B, beam_size, 1), dtype=torch.float32, device=dev)
-    new_met = torch.empty((B, beam_size), dtype=torch.int32, device=dev)
-    slp = seq_logprob.reshape(-1).float().contiguous()
-    if slp.numel() != B * cur:
-        raise _lib.GritHipError("seq_logprob has %d entries for %d x %d beams" % (slp.numel(), B, cur))
-    sm = pw = hist = None
-    if not first:
-        sm = seq_mask.reshape(-1).float().contiguous()
-        pw = prev_words.reshape(-1).contiguous()
-        if sm.numel() != B * cur or pw.numel() != B * cur or pw.dtype != torch.int64:
-            raise _lib.GritHipError("beam state does not match %d x %d beams" % (B, cur))
-    if con is None:
-        con, t = Constraints(0, 0, False, ()), 0
-    if t > 0:
-        hist = history.reshape(B * cur, -1)
-        if hist.shape[1] < t or hist.dtype != torch.int64 or hist.device != dev:
-            raise _lib.GritHipError("history does not hold %d words for %d x %d beams" % (t, B, cur))
-        hist = hist if hist.stride(1) == 1 else hist.contiguous()
-    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])  # host arrays: passed by value to the kernel
-    ids = (ctypes.c_int * max(1, len(con.suppress)))(*con.suppress)
-    with _lib.device_guard(dev):
-        st = L.grit_beam_step_forced_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), ld, _ptr(slp), _ptr(sm), _ptr(pw),
-                                         int(eos_idx), int(first), B, cur, V, beam_size, _ptr(fw), C, W, _ptr(met), _ptr(hist),
-                                         hist.stride(0) if hist is not None else 0, int(t), con.no_repeat_ngram,
-                                         int(con.no_repeat_word), int(t < con.min_len), ctypes.cast(ids, ctypes.c_void_p),
-                                         len(con.suppress), _ptr(ws), nbytes, _ptr(sel_beam), _ptr(sel_word), _ptr(new_lp),
-                                         _ptr(new_mask), _ptr(picked), _ptr(new_met), _lib.current_stream_ptr())
-    if st == _lib.ERR_UNSUPPORTED:
-        return None
-    _lib.check(st, "grit_beam_step_forced_f32")
-    return sel_beam, sel_word, new_lp, new_mask, picked, new_met
+    """The step with forced words of one map or of the mean of several on the device (two launches, nothing uploaded): force_words
+    [B, C, W] int64 and met [B, cur_beam] int32 (None: the first step) are device tensors.  Returns the five outputs of `beam_step`
+    and new_met [B, beam] int32, or None when the call is outside the kernel's limits (a beam above 8, fewer words than beams, more
+    than 8 sets or 4 words a set, and the limits of `beam_step_con`): the caller uses `beam_step_forced_host`."""
+    return _step(word_logprobs, seq_logprob, seq_mask, prev_words, eos_idx, beam_size, con, history, t, force_words=force_words,
+                 met=met)
+
+
+# ------------------------------------------------------------------------------------------------------ the decoders' choice
+def fused_step(maps, state, constraints, groups, force_words, met, history, timestep):
+    """The device step of a decoder, Transformer.iter (one map) and Ensemble.iter (one per member) alike: `state` is (seq_logprob,
+    seq_mask, prev_words, eos_idx, beam_size) with mask and words None at the first step, `history` [B, cur_beam, t] or None.
+    Returns what the chosen front returns, or None where the maps or the limits keep the step off the kernel: the caller then
+    takes the composed form."""
+    cur_beam, beam_size = maps[0].shape[1], state[-1]
+    if force_words is not None:
+        if supported_forced(maps, cur_beam, beam_size):
+            return beam_step_forced(maps, *state, force_words, met, history, timestep, constraints)
+    elif groups is not None:
+        if supported_div(maps, cur_beam, beam_size, groups.num_groups):
+            return beam_step_div(maps, *state, *groups, history, timestep, constraints)
+    elif supported_mean(maps, cur_beam, beam_size):
+        if constraints is not None:
+            return beam_step_con(maps, *state, history, timestep, constraints)
+        return beam_step_mean(maps, *state)
+    return None

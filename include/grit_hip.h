@@ -43,15 +43,15 @@
  *   grit_gemm_bf16_nt    <- nn.Linear + nn.GELU of Mlp (models/common/swin_model.py:31-37) and their autograd backward:
  *                           fc1 + bias + exact GELU in one pass; fc2's input gradient x GELU' + fc1's bias gradient in one pass
  *   grit_topk_rows_f32   <- Transformer.select (models/caption/transformer.py:184-188): sort of beam x vocabulary candidates
- *   grit_beam_step_f32   <- the body of Transformer.iter after the word log-probabilities (models/caption/transformer.py:208-240):
+ *   grit_beam_step       <- the body of Transformer.iter after the word log-probabilities (models/caption/transformer.py:208-240):
  *                           finished-beam masking, candidate scores, selection, beam / word split, score / mask / log-prob gathers
- *   grit_beam_step_mean_f32 <- the same after the averaged word log-probabilities of an ensemble (models/caption/ensemble.py:128-214:
+ *     n_maps > 1         <- the same after the averaged word log-probabilities of an ensemble (models/caption/ensemble.py:128-214:
  *                           torch.mean(torch.stack(per_model), 0) followed by the body of `iter`)
- *   grit_beam_step_con_f32 <- nothing in the reference (its search cannot be steered): the same step, of one map or of the mean,
+ *     its bans           <- nothing in the reference (its search cannot be steered): the same step, of one map or of the mean,
  *                           with a per-beam set of banned words applied while the candidates are scored
- *   grit_beam_step_div_f32 <- nothing in the reference (its beams are near-copies of one sentence): the same step for beam groups
+ *     its groups         <- nothing in the reference (its beams are near-copies of one sentence): the same step for beam groups
  *                           that are searched in turn, a group paying for every word an earlier group chose at this step
- *   grit_beam_step_forced_f32 <- nothing in the reference (its search cannot be made to mention a word): the same step with sets of
+ *     its forced words   <- nothing in the reference (its search cannot be made to mention a word): the same step with sets of
  *                           forced words per image, the beams of a step dealt out over banks by how many sets they have met
  *   grit_sample_step_f32 <- nothing in the reference (it decodes by beam search only): one word per row drawn from the tempered,
  *                           top-k / nucleus truncated word distribution, in integer arithmetic that a host form repeats exactly
@@ -86,7 +86,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 60
+#define GRIT_ABI_VERSION 61
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -767,9 +767,13 @@ int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t*
 
 /* ------------------------------------------------------------------------------------------------------
  * One beam-search step after the decoder (reference models/caption/transformer.py:208-240, `iter`), for B images with
- * cur_beam live beams each and a vocabulary of V words.  logp [B * cur_beam, V] float32 word log-probabilities (row stride ld),
- * seq_logprob [B * cur_beam] running scores, seq_mask [B * cur_beam] 1 while a beam is alive, prev_words [B * cur_beam] int64
- * the words chosen at the previous step (both ignored when first_step != 0: every beam alive).
+ * cur_beam live beams each and a vocabulary of V words: grit_beam_step(args, stream), every variant of the step through the one
+ * argument struct below.  A zero-initialised struct with the source, beam state, sizes, workspace and outputs filled is the plain
+ * step; the bans, the groups and the forced words are switched on by their own fields and described after it.
+ *
+ * Source, beam state, sizes, outputs.  logp [B * cur_beam, V] float32 word log-probabilities (row stride ld; maps[0] when
+ * n_maps == 1), seq_logprob [B * cur_beam] running scores, seq_mask [B * cur_beam] 1 while a beam is alive, prev_words
+ * [B * cur_beam] int64 the words chosen at the previous step (both ignored when first_step != 0: every beam alive).
  *     alive      = seq_mask * (prev_words != eos)
  *     candidate  = alive ? seq_logprob + logp : (word == 0 ? seq_logprob : -999)
  *     the k <= 8 best candidates of each image over (beam, word), best first; equal scores by ascending beam * V + word
@@ -777,35 +781,23 @@ int grit_topk_rows_f32(const float* x, long ld, int rows, int n, int k, int64_t*
  * picked_logprob = logp[sel_beam][sel_word] * alive.  Bit-identical to the reference's composed arithmetic.
  * workspace: grit_beam_step_workspace(B, cur_beam, k) bytes of device memory, no initialisation needed.  Limits: cur_beam * k <= 64
  * (16 at first_step), B <= 65535.  Two launches; safe to capture in a HIP graph.
- * ------------------------------------------------------------------------------------------------------ */
-long grit_beam_step_workspace(int B, int cur_beam, int k);
-int grit_beam_step_f32(const float* logp, long ld, const float* seq_logprob, const float* seq_mask, const int64_t* prev_words,
-                       int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace, long workspace_bytes,
-                       int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
-                       void* stream);
-
-/* ------------------------------------------------------------------------------------------------------
- * The beam-search step of an ensemble of n_maps <= 8 captioners (reference models/caption/ensemble.py:128-214): grit_beam_step_f32
- * applied to the average of n_maps word log-probability maps, each [B * cur_beam, V] float32 with the common row stride ld.
+ *
+ * The mean of n_maps <= 8 maps: the step of an ensemble of captioners (reference models/caption/ensemble.py:128-214), the plain
+ * step applied to the average of n_maps word log-probability maps, each [B * cur_beam, V] float32 with the common row stride ld.
  * maps is a HOST array of n_maps device pointers; they travel by value in the kernel arguments (no table to upload, nothing that
  * a captured HIP graph has to keep alive).  The average is formed in registers while the candidates are scored -- it is never
  * written -- and is bit-identical to torch.stack(maps).mean(0) on the device: per element, map m is added to accumulator m % 4
  * (each starting at 0), the four are summed as ((a0 + a1) + a2) + a3 and multiplied by float(N) / float(n_maps * N), N =
- * B * cur_beam * V.  picked_logprob is taken from that average.  Outputs, workspace (grit_beam_step_workspace), limits and the
- * order of ties are those of grit_beam_step_f32; with n_maps == 1 every output equals grit_beam_step_f32's bit for bit.
- * Two launches; safe to capture in a HIP graph.
- * ------------------------------------------------------------------------------------------------------ */
-int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                            const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, void* workspace,
-                            long workspace_bytes, int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask,
-                            float* picked_logprob, void* stream);
-
-/* ------------------------------------------------------------------------------------------------------
- * The beam-search step under constraints (no ancestor in the reference): grit_beam_step_f32 (n_maps == 1) or
- * grit_beam_step_mean_f32 (n_maps > 1; maps is the same HOST array of device pointers) with the candidate score of every banned
- * (beam, word) pair replaced by -inf.  Step t chooses word position t; history [B * cur_beam, t] int64 (row stride history_ld
- * elements; may be NULL when t == 0) holds the words h_0 .. h_{t-1} of every source beam.  A beam is live when first_step != 0 or
- * seq_mask * (prev_words != eos) != 0.  The banned set of a LIVE beam is the union of
+ * B * cur_beam * V.  picked_logprob is taken from that average.  Outputs, workspace, limits and the order of ties are those of
+ * one map.  n_maps == 1 reads maps[0] directly; the mean of one map, (0 + x) * 1.0f, is the same bits except that it turns a
+ * stored -0.0 into +0.0, so only the sign of a picked_logprob (or score) that is exactly zero could ever tell the two apart.
+ *
+ * Bans: the step under constraints (no ancestor in the reference), on when any of no_repeat_ngram > 0, no_repeat_word, ban_eos,
+ * n_suppress > 0 is set, and always on for a step with forced words; with all four off (and no forced words) t and history are
+ * not read and t is not checked against its limit.  The candidate score of every banned (beam, word) pair is replaced by -inf.
+ * Step t chooses word position t; history [B * cur_beam, t] int64 (row stride history_ld elements; may be NULL when t == 0) holds
+ * the words h_0 .. h_{t-1} of every source beam.  A beam is live when first_step != 0 or seq_mask * (prev_words != eos) != 0.
+ * The banned set of a LIVE beam is the union of
  *     ban_eos != 0          eos                                    (the caller sets it while t < its minimum length)
  *     suppress[0 .. n_suppress)  always; a HOST array of ids in [0, V), copied into the kernel arguments (nothing to upload,
  *                           nothing that a captured HIP graph has to keep alive)
@@ -815,71 +807,54 @@ int grit_beam_step_mean_f32(const float* const* maps, int n_maps, long ld, const
  * and a finished beam has none (it lives through word 0 alone).  History words outside [0, V) ban nothing and are never used as
  * an index (they still take part in the comparisons).  A banned candidate stays a candidate with its own index: with a small V and
  * many bans -inf candidates are selected, by ascending beam * V + word.  picked_logprob is the word's log-prob as stored, banned or
- * not.  With every constraint off the outputs equal those of grit_beam_step_f32 / grit_beam_step_mean_f32 bit for bit; the host
- * form is grit_amd/ops/beam.py: banned_words_host.  Outputs, workspace (grit_beam_step_workspace), limits and the order of ties
- * are those of grit_beam_step_f32.  Further limits (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form):
+ * not.  With every constraint off the plain stage 1 runs: a rule that bans nothing leaves every bit as it is.  The host
+ * form is grit_amd/ops/beam.py: banned_words_host.  Outputs, workspace, limits and the order of ties are those of the plain step.
+ * Further limits (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form):
  * 0 <= t <= GRIT_BEAM_MAX_HISTORY, n_suppress <= GRIT_BEAM_MAX_SUPPRESS, and a vocabulary slice (V / 8 at the first step, else
  * V / 2, rounded up to a multiple of 4) of at most GRIT_BEAM_MAX_SLICE words.  A suppress id outside [0, V), eos outside [0, V)
- * with ban_eos, negative t / no_repeat_ngram, or history == NULL with t > 0: GRIT_ERR_BAD_ARG.  Two launches, no atomics on
- * global memory, no host state; safe to capture in a HIP graph.
- * ------------------------------------------------------------------------------------------------------ */
-#define GRIT_BEAM_MAX_HISTORY 64
-#define GRIT_BEAM_MAX_SUPPRESS 16
-#define GRIT_BEAM_MAX_SLICE 65536
-int grit_beam_step_con_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                           const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                           const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos,
-                           const int* suppress, int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam,
-                           int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, void* stream);
-
-/* ------------------------------------------------------------------------------------------------------
- * The beam-search step of a DIVERSE (group) beam search with a Hamming penalty (Vijayakumar et al. 2016; no ancestor in the
- * reference): the k beams are `groups` groups of g = k / groups, group i owns the source rows and the output positions
- * [i * g, (i + 1) * g) (at the first step, cur_beam == 1, every group reads row 0), and within the step the groups are resolved
- * in the order 0 .. groups - 1 per image.  counts[w] = how many selections of groups 0 .. i - 1 in THIS step chose word w from a
- * LIVE source row (a finished row that survives through word 0 counts nothing; two beams choosing w count 2).  Group i scores
+ * with ban_eos, negative t / no_repeat_ngram, or history == NULL with t > 0: GRIT_ERR_BAD_ARG.  No atomics on global memory, no
+ * host state.
+ *
+ * Groups (groups >= 1; 0 is the plain merge): the step of a DIVERSE (group) beam search with a Hamming penalty (Vijayakumar et
+ * al. 2016; no ancestor in the reference).  The k beams are `groups` groups of g = k / groups, group i owns the source rows and
+ * the output positions [i * g, (i + 1) * g) (at the first step, cur_beam == 1, every group reads row 0), and within the step the
+ * groups are resolved in the order 0 .. groups - 1 per image.  counts[w] = how many selections of groups 0 .. i - 1 in THIS step
+ * chose word w from a LIVE source row (a finished row that survives through word 0 counts nothing; two beams choosing w count
+ * 2).  Group i scores
  *     live row j, word w:   seq_logprob[j] + (logp[j][w] - diversity * float(counts[w]))
- *                           one fp32 multiply, one fp32 subtract, the fp32 add of grit_beam_step_f32; never an fma
+ *                           one fp32 multiply, one fp32 subtract, the fp32 add of the plain step; never an fma
  *     finished row j:       seq_logprob[j] at word 0, -999 elsewhere (no penalty)
  *     banned (row, word):   -inf, penalised or not
  * and takes its g best of its g * V candidates, value descending, equal values by ascending row * V + word.  Outputs at position
  * i * g + r: sel_beam (the source row among all cur_beam), sel_word, new_seq_logprob = the PENALISED candidate score, new_seq_mask
  * = the source row's liveness, picked_logprob = the unpenalised logp[sel_beam][sel_word] * liveness.  logp is one map or the
- * mean of n_maps <= 8 maps exactly as in grit_beam_step_mean_f32 (a penalised score re-forms the mean the same way); the
- * constraint arguments are those of grit_beam_step_con_f32, and with all of them off (ban_eos, no_repeat_ngram, no_repeat_word,
- * n_suppress all 0) t and history are ignored.  With counts == 0 the score is grit_beam_step_f32's bit for bit, so groups == 1
- * gives the outputs of grit_beam_step_f32 / _mean_f32 / _con_f32.  The host form is grit_amd/ops/beam.py: beam_step_groups_host.
+ * mean of n_maps <= 8 maps exactly as above (a penalised score re-forms the mean the same way); the bans are those above.  With
+ * counts == 0 the score is the plain step's bit for bit, so groups == 1 gives the outputs of groups == 0 with the same source and
+ * bans, whatever the diversity.  The host form is grit_amd/ops/beam.py: beam_step_groups_host.
  *
  * The penalty only lowers candidates, and in one source row at most |P| <= k - g of them (P: the words chosen so far in this
  * step), so a group's g best of a row are among that row's UNPENALISED k best: stage 1 is the first launch of the plain /
  * constrained step with k entries per list, and all the sequential group logic is the second launch, one wave per image over the
- * same <= 128 candidates.  Workspace: grit_beam_step_workspace(B, cur_beam, k).  Limits (GRIT_ERR_UNSUPPORTED beyond them, the
+ * same <= 128 candidates.  Limits (GRIT_ERR_UNSUPPORTED beyond them, the
  * caller uses the host form): k <= 8, k % groups == 0, cur_beam == 1 or cur_beam == k, V >= k, diversity finite and >= 0,
- * B <= 65535, and with any constraint on the limits of grit_beam_step_con_f32.  groups < 1: GRIT_ERR_BAD_ARG.  Two launches,
- * no atomics on global memory, no host state, nothing uploaded; safe to capture in a HIP graph.
- * ------------------------------------------------------------------------------------------------------ */
-int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                           const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k, int groups,
-                           float diversity, const int64_t* history, long history_ld, int t, int no_repeat_ngram, int no_repeat_word,
-                           int ban_eos, const int* suppress, int n_suppress, void* workspace, long workspace_bytes,
-                           int64_t* sel_beam, int64_t* sel_word, float* new_seq_logprob, float* new_seq_mask, float* picked_logprob,
-                           void* stream);
-
-/* ------------------------------------------------------------------------------------------------------
- * The beam-search step with FORCED words (dynamic beam allocation, Post & Vilar 2018; no ancestor in the reference).
+ * B <= 65535, and with any ban on the limits of the bans.  groups < 0: GRIT_ERR_BAD_ARG.  No atomics on global memory, no host
+ * state, nothing uploaded.
+ *
+ * Forced words (force_words != NULL; NULL is not a forced step): the step with FORCED words (dynamic beam allocation, Post &
+ * Vilar 2018; no ancestor in the reference).  It has no groups: force_words with groups > 0 is GRIT_ERR_BAD_ARG.
  * force_words [B, n_sets, n_words] int64, padded with -1, lives on the device: set c of image b is the ids >= 0 of
  * force_words[b][c], a disjunction ("dog" or "dogs"); a set with no ids counts as met from the start.  Every beam carries met, an
  * int32 bitmask of the sets that its words so far have hit; full = all n_sets bits.  met_in [B * cur_beam] may be NULL (the first
  * step): every row of image b then starts from the mask of b's empty sets.  A step for an image with cur_beam source rows and
- * k = beam, liveness of a row exactly that of grit_beam_step_con_f32:
- *   1. Bans.  A live row has the bans of grit_beam_step_con_f32 (ban_eos, suppress, no_repeat_word, no_repeat_ngram), and <eos>
+ * k = beam, liveness of a row exactly that of the bans:
+ *   1. Bans.  A live row has the bans above (ban_eos, suppress, no_repeat_word, no_repeat_ngram), and <eos>
  *      is banned in addition while met != full.
  *   2. Candidates A.  Row j contributes its k best candidates under the constrained step's scoring: a live row scores
  *      seq_logprob[j] + logp[j][w] (one fp32 add; -inf where banned), ties to the ascending word -- what stage 1 of that step
  *      leaves in the workspace.  A finished row contributes only its word-0 candidate with the score seq_logprob[j]; its -999
  *      siblings are not candidates here.
  *   3. Candidates F.  A live row j also contributes (j, w) for every w of a set that row j has not met and that is not banned for
- *      that row, scored by the same single add (for n_maps > 1 on the mean re-formed exactly as grit_beam_step_mean_f32 forms
+ *      that row, scored by the same single add (for n_maps > 1 on the mean re-formed exactly as stage 1 forms
  *      it).  Duplicates of (j, w) are kept once; their scores are identical bits.
  *   4. Banks.  met'(j, w) = met[j] | {c : w in set c} for a live row, met[j] for a finished row; bank = popcount(met'); a
  *      candidate that scores -inf goes to bank -1.
@@ -894,23 +869,65 @@ int grit_beam_step_div_f32(const float* const* maps, int n_maps, long ld, const 
  * n_sets steps and no forced word under a ban the best hypothesis of the top bank holds a word of every set; that it also reaches
  * <eos> is not promised.  The host form is grit_amd/ops/beam.py: beam_step_forced_host.
  *
- * Stage 1 is the first launch of grit_beam_step_con_f32 (k entries per list) with the one per-row addition of the <eos> ban;
+ * Stage 1 is the first launch of the step under bans (k entries per list) with the one per-row addition of the <eos> ban;
  * stage 2 is one workgroup per image over at most cur_beam * (k + n_sets * n_words) <= 320 candidates in LDS: it gathers the
- * forced candidates from logp, tests them against the row's ban rules, removes duplicates, banks, ranks and stores.  Workspace:
- * grit_beam_step_workspace(B, cur_beam, k).  Limits (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form): k <= 8,
+ * forced candidates from logp, tests them against the row's ban rules, removes duplicates, banks, ranks and stores.  Limits
+ * (GRIT_ERR_UNSUPPORTED beyond them, the caller uses the host form): k <= 8,
  * cur_beam == 1 or cur_beam == k, V >= k, n_sets <= GRIT_BEAM_MAX_FORCED_SETS, n_words <= GRIT_BEAM_MAX_FORCED_WORDS, and the
- * limits of grit_beam_step_con_f32.  n_sets < 1, n_words < 1 or force_words / new_met == NULL: GRIT_ERR_BAD_ARG.  Forced ids
- * outside [0, V) are skipped.  Two launches, no atomics on global memory, no host state, nothing uploaded; safe to capture in a
- * HIP graph.
+ * limits of the bans.  n_sets < 1, n_words < 1, or new_met == NULL: GRIT_ERR_BAD_ARG; new_met is required exactly when
+ * force_words is set and is not written otherwise.  Forced ids outside [0, V) are skipped.  No atomics on global memory, no host
+ * state, nothing uploaded.
+ *
+ * Every variant: workspace = grit_beam_step_workspace(B, cur_beam, k) bytes, two launches, safe to capture in a HIP graph.  A
+ * refusal writes nothing to the outputs.  Statuses are decided in this order: GRIT_ERR_BAD_ARG for a NULL maps, a size or n_maps
+ * <= 0, a negative rule, groups or t, a ban without its history, eos or suppress pointer, forced words with groups or without
+ * their sizes or new_met; GRIT_ERR_UNSUPPORTED beyond a limit of the source (n_maps), the bans (t, n_suppress), the groups or the
+ * forced words; GRIT_ERR_BAD_ARG for a NULL map, state, workspace or output pointer, ld < V or a suppress id outside [0, V);
+ * GRIT_ERR_UNSUPPORTED beyond a limit of the plain step or of the bans' slice; GRIT_ERR_BAD_ARG for a workspace that is too small.
  * ------------------------------------------------------------------------------------------------------ */
+#define GRIT_BEAM_MAX_HISTORY 64
+#define GRIT_BEAM_MAX_SUPPRESS 16
+#define GRIT_BEAM_MAX_SLICE 65536
 #define GRIT_BEAM_MAX_FORCED_SETS 8
 #define GRIT_BEAM_MAX_FORCED_WORDS 4
-int grit_beam_step_forced_f32(const float* const* maps, int n_maps, long ld, const float* seq_logprob, const float* seq_mask,
-                              const int64_t* prev_words, int eos, int first_step, int B, int cur_beam, int V, int k,
-                              const int64_t* force_words, int n_sets, int n_words, const int* met_in, const int64_t* history,
-                              long history_ld, int t, int no_repeat_ngram, int no_repeat_word, int ban_eos, const int* suppress,
-                              int n_suppress, void* workspace, long workspace_bytes, int64_t* sel_beam, int64_t* sel_word,
-                              float* new_seq_logprob, float* new_seq_mask, float* picked_logprob, int* new_met, void* stream);
+typedef struct grit_beam_step_args {
+    /* source */
+    const float* const* maps;  /* HOST array of n_maps device pointers */
+    int n_maps;
+    long ld;
+    /* beam state */
+    const float* seq_logprob;
+    const float* seq_mask;
+    const int64_t* prev_words;
+    int eos, first_step;
+    /* sizes */
+    int B, cur_beam, V, k;
+    /* bans */
+    const int64_t* history;
+    long history_ld;
+    int t, no_repeat_ngram, no_repeat_word, ban_eos;
+    const int* suppress;  /* HOST array of n_suppress ids */
+    int n_suppress;
+    /* groups */
+    int groups;  /* 0: the plain merge */
+    float diversity;
+    /* forced words */
+    const int64_t* force_words;  /* NULL: not a forced step */
+    int n_sets, n_words;
+    const int* met_in;
+    /* workspace */
+    void* workspace;
+    long workspace_bytes;
+    /* outputs */
+    int64_t* sel_beam;
+    int64_t* sel_word;
+    float* new_seq_logprob;
+    float* new_seq_mask;
+    float* picked_logprob;
+    int* new_met;
+} grit_beam_step_args;
+long grit_beam_step_workspace(int B, int cur_beam, int k);
+int grit_beam_step(const grit_beam_step_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * One step of sampled decoding after the decoder (no ancestor in the reference, whose only decoder is beam search): one word per

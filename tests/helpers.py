@@ -49,6 +49,31 @@ def result_manager():
     return torch.multiprocessing.get_context("spawn").Manager()
 
 
+BEAM_STEP_OUTPUTS = ("sel_beam", "sel_word", "new_seq_logprob", "new_seq_mask", "picked_logprob", "new_met")
+
+
+def beam_step_raw(**fields):
+    """grit_beam_step as the C ABI states it: a zero-initialised grit_beam_step_args with `fields` set by name, the status back after
+    a synchronise.  A tensor gives its address and None is NULL; `maps` (a list of tensors, n_maps = its length unless given) and
+    `suppress` (a list of ids, n_suppress likewise) become the host arrays that the struct points to."""
+    import ctypes
+    from grit_amd import lib
+    args, keep = lib.BeamStepArgs(), []
+    names = {name for name, _ in lib.BeamStepArgs._fields_}
+    for name, value in fields.items():
+        assert name in names, name
+        if name in ("maps", "suppress") and value is not None:
+            items = [m.data_ptr() for m in value] if name == "maps" else list(value)
+            keep.append(((ctypes.c_void_p if name == "maps" else ctypes.c_int) * max(1, len(items)))(*items))
+            if "n_" + name not in fields:
+                setattr(args, "n_" + name, len(items))
+            value = ctypes.addressof(keep[-1])
+        setattr(args, name, value.data_ptr() if torch.is_tensor(value) else value)
+    status = lib.load().grit_beam_step(ctypes.byref(args), lib.current_stream_ptr())
+    torch.cuda.synchronize()
+    return status
+
+
 def t(a, dtype=None, device="cpu"):
     x = torch.from_numpy(np.ascontiguousarray(a))
     return (x if dtype is None else x.to(dtype)).to(device)

@@ -68,6 +68,19 @@ def test_type_mapping_of_pinned_prototypes():
     assert functions["grit_status_string"] == (ctypes.c_char_p, [I])
     assert functions["grit_beam_step_workspace"] == (L, [I, I, I])
     assert functions["grit_abi_version"] == (I, [])
+    assert functions["grit_beam_step"] == (I, [P, P])  # the argument struct and the stream
+    assert not {"grit_beam_step_f32", "grit_beam_step_mean_f32", "grit_beam_step_con_f32", "grit_beam_step_div_f32",
+                "grit_beam_step_forced_f32"} & set(functions)
+    assert abi.read().structs["grit_beam_step_args"] == [
+        ("maps", P), ("n_maps", I), ("ld", L),
+        ("seq_logprob", P), ("seq_mask", P), ("prev_words", P), ("eos", I), ("first_step", I),
+        ("B", I), ("cur_beam", I), ("V", I), ("k", I),
+        ("history", P), ("history_ld", L), ("t", I), ("no_repeat_ngram", I), ("no_repeat_word", I), ("ban_eos", I), ("suppress", P),
+        ("n_suppress", I),
+        ("groups", I), ("diversity", F),
+        ("force_words", P), ("n_sets", I), ("n_words", I), ("met_in", P),
+        ("workspace", P), ("workspace_bytes", L),
+        ("sel_beam", P), ("sel_word", P), ("new_seq_logprob", P), ("new_seq_mask", P), ("picked_logprob", P), ("new_met", P)]
     assert lib.SIGNATURES["grit_wgrad_tn"] == functions["grit_wgrad_tn"][1]
     loaded = lib.load()
     assert loaded.grit_beam_step_workspace.restype is L and loaded.grit_status_string.restype is ctypes.c_char_p

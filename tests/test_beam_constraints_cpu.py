@@ -1,4 +1,4 @@
-"""Beam-search constraints without a GPU: the C ABI of grit_beam_step_con_f32, the host statement of the banned set
+"""Beam-search constraints without a GPU: the C ABI of the bans of grit_beam_step, the host statement of the banned set
 (grit_amd/ops/beam.py: banned_words_host) against a brute-force enumerator, Transformer.forward / Ensemble.forward with
 min_len, no_repeat_ngram, no_repeat_word, suppress and length_penalty on fixture G15 under the oracle ops, and what is refused."""
 import ctypes
@@ -17,13 +17,15 @@ V_SMALL = 11  # an alphabet in which repeats abound
 def test_symbol_and_constants():
     from grit_amd import abi, lib
     a = abi.read()
-    assert "grit_beam_step_con_f32" in a.functions
-    assert len(a.functions["grit_beam_step_con_f32"][1]) == len(a.functions["grit_beam_step_mean_f32"][1]) + 8
-    assert "grit_beam_step_con_f32" in lib.SIGNATURES
+    assert "grit_beam_step" in a.functions and "grit_beam_step_con_f32" not in a.functions
+    names = [name for name, _ in a.structs["grit_beam_step_args"]]  # the eight fields of the bans, in the struct of the one step
+    at = names.index("history")
+    assert names[at:at + 8] == ["history", "history_ld", "t", "no_repeat_ngram", "no_repeat_word", "ban_eos", "suppress", "n_suppress"]
+    assert "grit_beam_step" in lib.SIGNATURES
     assert a.constants["GRIT_BEAM_MAX_HISTORY"] == lib.BEAM_MAX_HISTORY == 64
     assert a.constants["GRIT_BEAM_MAX_SUPPRESS"] == lib.BEAM_MAX_SUPPRESS == 16
-    assert hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step_con_f32")
-    assert lib.load().grit_abi_version() == a.version >= 54
+    assert hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step")
+    assert lib.load().grit_abi_version() == a.version >= 61
 
 
 # ---------------------------------------------------------------------------------------------------------------- host form

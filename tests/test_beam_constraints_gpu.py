@@ -1,14 +1,13 @@
-"""grit_beam_step_con_f32 on the device: every check is bit-equality of all five outputs against the composed torch form on the
+"""grit_beam_step with its bans on the device: every check is bit-equality of all five outputs against the composed torch form on the
 same device (the reference's step arithmetic, grit_amd/ops/beam.py: banned_words_host as one masked_fill(-inf), a stable descending
 sort), at the slice boundaries, on the scalar load path, for the ensemble mean and at the limits; then the constrained decode of
 the fixture-G15 model: fused step against composed step, graph replay against the eager loop, one graph per constraint tuple."""
 import copy
-import ctypes
 
 import pytest
 import torch
 
-from tests.helpers import load, t
+from tests.helpers import BEAM_STEP_OUTPUTS, beam_step_raw, load, t
 from tests.test_beam_constraints_cpu import ALPHA, CASES, violations
 from tests.test_sample_cpu import EOS, FEATS, decode, g15_model
 
@@ -51,7 +50,7 @@ def composed(maps, seq_lp, seq_mask, prev, eos, beam, hist, step, c):
 
 
 def launch(maps, seq_lp, seq_mask, prev, eos, beam, hist, step, c, hist_ld=None):
-    """grit_beam_step_con_f32 as the C ABI states it: maps [B, cur, V] with any row stride (rows evenly spaced, words adjacent).
+    """grit_beam_step with the bans as the C ABI states it: maps [B, cur, V] with any row stride (rows evenly spaced, words adjacent).
     Returns the status and the five outputs."""
     from grit_amd import lib
     L = lib.load()
@@ -67,17 +66,13 @@ def launch(maps, seq_lp, seq_mask, prev, eos, beam, hist, step, c, hist_ld=None)
     slp = seq_lp.reshape(-1).contiguous()
     sm = None if first else seq_mask.reshape(-1).contiguous()
     pw = None if first else prev.reshape(-1).contiguous()
-    table = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
-    ids = (ctypes.c_int * max(1, len(c.suppress)))(*c.suppress)
     if hist is not None:
         assert hist.dtype == torch.int64 and hist.stride(-1) == 1
         hist_ld = hist_ld or hist.stride(-2)
-    st = L.grit_beam_step_con_f32(ctypes.cast(table, ctypes.c_void_p), len(maps), maps[0].stride(1), lib.ptr(slp), lib.ptr(sm),
-                                  lib.ptr(pw), eos, int(first), B, cur, V, beam, lib.ptr(hist), hist_ld or 0, step,
-                                  c.no_repeat_ngram, int(c.no_repeat_word), int(step < c.min_len),
-                                  ctypes.cast(ids, ctypes.c_void_p), len(c.suppress), lib.ptr(ws), nbytes,
-                                  *[lib.ptr(o) for o in out], lib.current_stream_ptr())
-    torch.cuda.synchronize()
+    st = beam_step_raw(maps=maps, ld=maps[0].stride(1), seq_logprob=slp, seq_mask=sm, prev_words=pw, eos=eos, first_step=int(first),
+                       B=B, cur_beam=cur, V=V, k=beam, history=hist, history_ld=hist_ld or 0, t=step,
+                       no_repeat_ngram=c.no_repeat_ngram, no_repeat_word=int(c.no_repeat_word), ban_eos=int(step < c.min_len),
+                       suppress=c.suppress, workspace=ws, workspace_bytes=nbytes, **dict(zip(BEAM_STEP_OUTPUTS, out)))
     return st, tuple(out)
 
 
@@ -237,7 +232,8 @@ def test_bad_arguments_write_nothing():
     from grit_amd import lib
     maps, seq_lp, seq_mask, prev = state(2, 5, 100, 51)
     hist = torch.zeros((2, 5, 3), dtype=torch.int64, device=DEV)
-    for c, kw in ((con(suppress=(100,)), {}), (con(suppress=(-1,)), {}), (con(no_repeat_ngram=-1), {}), (con(), dict(hist_ld=2))):
+    for c, kw in ((con(suppress=(100,)), {}), (con(suppress=(-1,)), {}), (con(no_repeat_ngram=-1), {}),
+                  (con(no_repeat_word=True), dict(hist_ld=2))):  # a live rule: with none, t and history are not read
         st, out = launch(maps, seq_lp, seq_mask, prev, EOS, 5, hist, 3, c, **kw)
         assert st == lib.ERR_BAD_ARG and all((o == -7).all() for o in out), c
     st, out = launch(maps, seq_lp, seq_mask, prev, EOS, 5, None, 3, con(no_repeat_ngram=2))

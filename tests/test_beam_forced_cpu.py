@@ -21,11 +21,14 @@ def test_symbol_and_constants():
     a = abi.read()
     assert a.constants["GRIT_BEAM_MAX_FORCED_SETS"] == lib.BEAM_MAX_FORCED_SETS == 8
     assert a.constants["GRIT_BEAM_MAX_FORCED_WORDS"] == lib.BEAM_MAX_FORCED_WORDS == 4
-    # the constrained step's arguments, the sets (pointer, C, W), met_in and new_met
-    assert len(a.functions["grit_beam_step_forced_f32"][1]) == len(a.functions["grit_beam_step_con_f32"][1]) + 5
-    assert a.functions["grit_beam_step_forced_f32"][1][12:16] == [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    assert hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step_forced_f32")
-    assert lib.load().grit_abi_version() == a.version >= 59
+    # the sets (pointer, C, W) and met_in in the argument struct of the one step, new_met behind the other outputs
+    fields = a.structs["grit_beam_step_args"]
+    at = [name for name, _ in fields].index("force_words")
+    assert fields[at:at + 4] == [("force_words", ctypes.c_void_p), ("n_sets", ctypes.c_int), ("n_words", ctypes.c_int),
+                                 ("met_in", ctypes.c_void_p)]
+    assert fields[-1] == ("new_met", ctypes.c_void_p)
+    assert "grit_beam_step_forced_f32" not in a.functions and hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step")
+    assert lib.load().grit_abi_version() == a.version >= 61
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule

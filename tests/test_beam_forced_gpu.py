@@ -1,15 +1,14 @@
-"""grit_beam_step_forced_f32 on the device: every check is bit-equality of all six outputs against the host statement of the step
-(grit_amd/ops/beam.py: beam_step_forced_host, itself checked against a loop-per-candidate reference in
+"""grit_beam_step with forced words on the device: every check is bit-equality of all six outputs against the host statement of
+the step (grit_amd/ops/beam.py: beam_step_forced_host, itself checked against a loop-per-candidate reference in
 tests/test_beam_forced_cpu.py) on the same device tensors -- at both list lengths of stage 1, at the 320-candidate ceiling, with
 duplicates, words in two sets, banned forced words, finished rows and empty sets, for a strided map and the ensemble mean; empty
 sets against the constrained step; the limits; then the decode of the fixture-G15 model with forced words from a captured graph
 against the eager loop on the host form."""
-import ctypes
 
 import pytest
 import torch
 
-from tests.helpers import load, t
+from tests.helpers import BEAM_STEP_OUTPUTS, beam_step_raw, load, t
 from tests.test_beam_forced_cpu import sets_for
 from tests.test_sample_cpu import EOS, FEATS, decode, g15_model
 
@@ -201,7 +200,7 @@ def test_two_calls_give_the_same_bits():
 @pytest.mark.parametrize("B,beam,V", [(3, 5, 10201), (2, 8, 257), (2, 6, 64)])
 def test_empty_sets_are_the_constrained_step(B, beam, V):
     """every set empty, and one live row per image so that the constrained step has no -999 candidate to select: the first five
-    outputs are those of grit_beam_step_con_f32 and of the plain step"""
+    outputs are those of the constrained step and of the plain step"""
     from grit_amd.ops.beam import beam_step, beam_step_con, beam_step_forced, constraints
     con = constraints(V, min_len=5, no_repeat_ngram=2, no_repeat_word=True, suppress=(0, 5))
     gen = torch.Generator(device=DEV).manual_seed(V)
@@ -242,13 +241,10 @@ def test_outside_the_limits_nothing_is_launched(monkeypatch):
     ws = torch.empty(1 << 16, dtype=torch.uint8, device=DEV)
     for (maps, seq_lp, seq_mask, prev, fw, met), beam, V, step, ngram in ((wide, 9, 1003, 0, 0), (small, 6, 5, 0, 0), (late, 6, 1003, 65, 2),
                                                                          (sets, 6, 1003, 0, 0), (words, 6, 1003, 0, 0)):
-        table = (ctypes.c_void_p * 1)(maps[0].data_ptr())
-        ids = (ctypes.c_int * 1)(0)
-        st = L.grit_beam_step_forced_f32(ctypes.cast(table, ctypes.c_void_p), 1, V, lib.ptr(seq_lp), lib.ptr(seq_mask), lib.ptr(prev), EOS,
-                                         0, 2, beam, V, beam, lib.ptr(fw), fw.shape[1], fw.shape[2], lib.ptr(met), lib.ptr(hist), 65,
-                                         step, ngram, 0, 0, ctypes.cast(ids, ctypes.c_void_p), 0, lib.ptr(ws), ws.numel(),
-                                         *[lib.ptr(o) for o in out], lib.current_stream_ptr())
-        torch.cuda.synchronize()
+        st = beam_step_raw(maps=maps[:1], ld=V, seq_logprob=seq_lp, seq_mask=seq_mask, prev_words=prev, eos=EOS, first_step=0, B=2,
+                           cur_beam=beam, V=V, k=beam, force_words=fw, n_sets=fw.shape[1], n_words=fw.shape[2], met_in=met,
+                           history=hist, history_ld=65, t=step, no_repeat_ngram=ngram, suppress=[0], n_suppress=0, workspace=ws,
+                           workspace_bytes=ws.numel(), **dict(zip(BEAM_STEP_OUTPUTS, out)))
         assert st == lib.ERR_UNSUPPORTED and all((o == -7).all() for o in out), (beam, V, step, tuple(fw.shape))
     # ... and the wrapper does not even call it
     monkeypatch.setattr(lib, "load", lambda: pytest.fail("the library was called"))

@@ -20,10 +20,10 @@ def test_symbol():
     import ctypes
     from grit_amd import abi, lib
     a = abi.read()
-    assert len(a.functions["grit_beam_step_div_f32"][1]) == len(a.functions["grit_beam_step_con_f32"][1]) + 2
-    assert a.functions["grit_beam_step_div_f32"][1][12:14] == [ctypes.c_int, ctypes.c_float]  # groups, diversity
-    assert hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step_div_f32")
-    assert lib.load().grit_abi_version() == a.version >= 56
+    fields = dict(a.structs["grit_beam_step_args"])  # the argument struct of the one step
+    assert (fields["groups"], fields["diversity"]) == (ctypes.c_int, ctypes.c_float)
+    assert "grit_beam_step_div_f32" not in a.functions and hasattr(ctypes.CDLL(lib.LIB_PATH), "grit_beam_step")
+    assert lib.load().grit_abi_version() == a.version >= 61
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rule

@@ -1,5 +1,5 @@
-"""grit_beam_step_div_f32 on the device: every check is bit-equality of all five outputs against the host statement of the grouped
-step (grit_amd/ops/beam.py: beam_step_groups_host, itself checked against a loop-per-candidate reference in
+"""grit_beam_step with beam groups on the device: every check is bit-equality of all five outputs against the host statement of
+the grouped step (grit_amd/ops/beam.py: beam_step_groups_host, itself checked against a loop-per-candidate reference in
 tests/test_beam_groups_cpu.py) on the same device tensors -- at both list lengths of stage 1, at the 128-candidate ceiling, on the
 scalar and the 16-byte load path, with slices that are empty at the first step, under constraints and for the ensemble mean; one
 group against the plain and the constrained step; the limits; then the grouped decode of the fixture-G15 model from a captured
@@ -9,7 +9,7 @@ import copy
 import pytest
 import torch
 
-from tests.helpers import load, t
+from tests.helpers import BEAM_STEP_OUTPUTS, beam_step_raw, load, t
 from tests.test_sample_cpu import EOS, FEATS, decode, g15_model
 
 pytestmark = pytest.mark.gpu
@@ -176,15 +176,11 @@ def test_outside_the_limits_nothing_is_launched(monkeypatch):
     out = [torch.full((2, 9), -7, dtype=torch.int64, device=DEV), torch.full((2, 9), -7, dtype=torch.int64, device=DEV)] + \
         [torch.full((2, 9, 1), -7.0, device=DEV) for _ in range(3)]
     ws = torch.empty(1 << 16, dtype=torch.uint8, device=DEV)
-    import ctypes
     for (maps, seq_lp, seq_mask, prev), beam, V, step, ngram in ((wide, 9, 1003, 0, 0), (small, 6, 5, 0, 0), (late, 6, 1003, 65, 2)):
-        table = (ctypes.c_void_p * 1)(maps[0].data_ptr())
-        ids = (ctypes.c_int * 1)(0)
-        st = L.grit_beam_step_div_f32(ctypes.cast(table, ctypes.c_void_p), 1, V, lib.ptr(seq_lp), lib.ptr(seq_mask), lib.ptr(prev), EOS,
-                                      0, 2, beam, V, beam, 3, 0.5, lib.ptr(hist), 65, step, ngram, 0, 0,
-                                      ctypes.cast(ids, ctypes.c_void_p), 0, lib.ptr(ws), ws.numel(), *[lib.ptr(o) for o in out],
-                                      lib.current_stream_ptr())
-        torch.cuda.synchronize()
+        st = beam_step_raw(maps=maps[:1], ld=V, seq_logprob=seq_lp, seq_mask=seq_mask, prev_words=prev, eos=EOS, first_step=0, B=2,
+                           cur_beam=beam, V=V, k=beam, groups=3, diversity=0.5, history=hist, history_ld=65, t=step,
+                           no_repeat_ngram=ngram, suppress=[0], n_suppress=0, workspace=ws, workspace_bytes=ws.numel(),
+                           **dict(zip(BEAM_STEP_OUTPUTS, out)))
         assert st == lib.ERR_UNSUPPORTED and all((o == -7).all() for o in out), (beam, V, step)
     # ... and the wrapper does not even call it
     monkeypatch.setattr(lib, "load", lambda: pytest.fail("the library was called"))

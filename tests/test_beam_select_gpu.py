@@ -54,7 +54,7 @@ def test_strided_and_unaligned_rows():
     assert torch.equal(idx, si[:, :5]) and torch.equal(val, sv[:, :5])
 
 
-# ------------------------------------------------------------------ grit_beam_step_f32: one whole step of Transformer.iter
+# ---------------------------------------------------------------------- grit_beam_step: one whole step of Transformer.iter
 def _composed_step(word_logprob, seq_logprob, seq_mask, prev_words, eos, beam, first):
     """The reference's arithmetic, op by op (models/caption/transformer.py:208-240)."""
     B, cur, V = word_logprob.shape

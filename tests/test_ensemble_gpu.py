@@ -1,5 +1,5 @@
-"""Ensemble beam search on the device: grit_beam_step_mean_f32 against the torch composition of the reference's step, the
-graphed and eager ensemble decode against fixture G16 and against its members, and the entry points."""
+"""Ensemble beam search on the device: grit_beam_step on the mean of several maps against the torch composition of the
+reference's step, the graphed and eager ensemble decode against fixture G16 and against its members, and the entry points."""
 import copy
 import json
 import subprocess
@@ -97,7 +97,7 @@ def test_mean_step_refusals():
     maps = [torch.zeros(2, 1, 11, device=DEV) for _ in range(9)]
     with torch.no_grad():
         assert beam_ops.supported_mean(maps[:8], 1, 5) and not beam_ops.supported_mean(maps, 1, 5)
-        with pytest.raises(lib.GritHipError, match="grit_beam_step_mean_f32"):
+        with pytest.raises(lib.GritHipError, match="grit_beam_step failed"):
             beam_ops.beam_step_mean(maps, torch.zeros(2, 1, 1, device=DEV), None, None, 3, 5)
 
 

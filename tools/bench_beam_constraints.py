@@ -1,5 +1,5 @@
-"""Beam search under constraints on one GPU: the constrained step (grit_beam_step_con_f32) against the plain step
-(grit_beam_step_f32), and the whole decode with and without constraints.
+"""Beam search under constraints on one GPU: the constrained step (grit_beam_step with bans) against the plain step
+(grit_beam_step), and the whole decode with and without constraints.
 
     python tools/bench_beam_constraints.py step    [--batch 64] [--vocab 10201] [--iters 200] [--legs 5] [--out FILE]
     python tools/bench_beam_constraints.py kernel  [--batch 64] [--vocab 10201] [--iters 50]   (run it under rocprofv3 --kernel-trace)

@@ -1,5 +1,5 @@
-"""Beam search with forced words on one GPU: the step with forced words (grit_beam_step_forced_f32) against the plain step
-(grit_beam_step_f32), the constrained step (grit_beam_step_con_f32) and its own host form (grit_amd/ops/beam.py:
+"""Beam search with forced words on one GPU: the step with forced words (grit_beam_step with force_words) against the plain step
+(grit_beam_step), the constrained step (grit_beam_step with bans) and its own host form (grit_amd/ops/beam.py:
 beam_step_forced_host), and the whole decode with and without forced words.
 
     python tools/bench_beam_forced.py step    [--batch 64] [--vocab 10201] [--iters 200] [--legs 5] [--out FILE]

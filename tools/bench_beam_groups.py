@@ -1,4 +1,4 @@
-"""Diverse (group) beam search on one GPU: the grouped step (grit_beam_step_div_f32) against the plain step (grit_beam_step_f32)
+"""Diverse (group) beam search on one GPU: the grouped step (grit_beam_step with groups) against the plain step (grit_beam_step)
 and against its host form (grit_amd/ops/beam.py: beam_step_groups_host), and the whole decode with and without groups.
 
     python tools/bench_beam_groups.py step    [--batch 64] [--vocab 10201] [--iters 200] [--legs 5] [--out FILE]

@@ -1,5 +1,5 @@
 """Ensemble beam search on one GPU: ms per batch of 64 images (beam 5, 20 steps, bf16 weights, decode from cached features)
-for K = 1 ... 4 members next to the single model, and the fused ensemble step grit_beam_step_mean_f32 alone at BASELINE
+for K = 1 ... 4 members next to the single model, and the fused ensemble step grit_beam_step with n_maps > 1 alone at BASELINE
 config 5's size (B 64, beam 5, V 10 201) against its HBM bound.
 
     python tools/bench_ensemble.py [--batch 64] [--iters 10] [--max-models 4]
@@ -102,7 +102,7 @@ def main():
         us = _kernel_us(B, 5, V, K)
         nbytes = K * B * 5 * V * 4  # every map read once (the candidates and the average stay in registers)
         bound = nbytes / (a.hbm_tbs * 1e12) * 1e6
-        print(json.dumps({"what": "grit_beam_step_mean_f32 (two launches)", "models": K, "B": B, "beam": 5, "V": V,
+        print(json.dumps({"what": "grit_beam_step with n_maps > 1 (two launches)", "models": K, "B": B, "beam": 5, "V": V,
                           "bytes_read": nbytes, "us": round(us, 2), "hbm_bound_us": round(bound, 2),
                           "fraction_of_bound": round(bound / us, 3)}))
 

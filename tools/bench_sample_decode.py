@@ -7,7 +7,7 @@ against beam search, and the self-critical step with sampled captions against th
     python tools/bench_sample_decode.py sc     [--batch 16] [--iters 3] [--legs 3] [--out FILE]
 
 `step` times one step from device events in alternating legs: the kernel, the torch composition (softmax(logp / T) -> multinomial; with
-truncation sort -> cumsum -> mask -> multinomial) and, for orientation, grit_beam_step_f32 at the same rows.  The spread of a leg
+truncation sort -> cumsum -> mask -> multinomial) and, for orientation, grit_beam_step at the same rows.  The spread of a leg
 (largest minus smallest leg mean) is printed next to every mean: a difference inside it is no difference.  Every mode prints JSON
 lines; a measurement path that finds no GPU fails."""
 import argparse
