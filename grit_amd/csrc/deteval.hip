@@ -12,6 +12,7 @@
 // category's detections in order and, for each, the category's ground truths -- the regular ones first, the ignored ones after
 // them, which is the stable "ignored last" order without a sort.  IoUs are computed on the fly (a [100, 512] float64 table does
 // not fit in LDS).  "Ground truth g is taken at (range a, threshold t)" is bit t of an LDS word per (a, g): a bit has one writer.
+// The Visual Genome protocol's matching (grit_det_voc_img, one threshold, no ignored rows) is described at its kernel below.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -311,6 +312,84 @@ __global__ __launch_bounds__(kThreads) void det_eval_img_kernel(const float* __r
     if (threadIdx.x == 0) seen[img] = 1;
 }
 
+// ---- per-image matching of the Visual Genome protocol (PASCAL VOC at one threshold) --------------------------------------------
+
+// Overlap of a detection's corners d and a ground-truth row g (x, y, w, h), both with the protocol's +1 pixel convention.
+__device__ inline double voc_overlap(const double* __restrict__ d, const double* __restrict__ g) {
+#pragma clang fp contract(off)
+    const double g2 = g[0] + g[2], g3 = g[1] + g[3];
+    const double iw = fmax(fmin(g2, d[2]) - fmax(g[0], d[0]) + 1.0, 0.0);
+    const double ih = fmax(fmin(g3, d[3]) - fmax(g[1], d[1]) + 1.0, 0.0);
+    const double inters = iw * ih;
+    const double uni = (d[2] - d[0] + 1.0) * (d[3] - d[1] + 1.0) + (g2 - g[0] + 1.0) * (g3 - g[1] + 1.0) - inters;
+    return inters / uni;
+}
+
+// A thread per detection finds (ovmax, jmax) over its class's rows -- independent of every other detection.  "True positive or
+// duplicate" is then whether an earlier detection of the class holds the same row above the threshold: a first-occurrence test on
+// the LDS copies, no state carried from detection to detection.
+__global__ __launch_bounds__(kThreads) void det_voc_img_kernel(const float* __restrict__ scores, const int64_t* __restrict__ labels,
+                                                               const float* __restrict__ boxes, const int32_t* __restrict__ slot, int N,
+                                                               grit_det_gt gt, double thr, uint8_t* __restrict__ rec_flag,
+                                                               int32_t* __restrict__ rec_gt, double* __restrict__ rec_iou,
+                                                               float* __restrict__ rec_score, int32_t* __restrict__ rec_label,
+                                                               uint8_t* __restrict__ seen) {
+    __shared__ double s_ov[kTop];
+    __shared__ int s_label[kTop], s_j[kTop];
+    const long b = blockIdx.x;
+    const int img = slot[b];
+    if (img < 0 || img >= gt.n_img) return;
+    const int first = gt.img_off[img], G = gt.img_off[img + 1] - first;
+    if (first < 0 || G < 0 || G > kSide) return;
+    for (int n = threadIdx.x; n < N; n += kThreads) {
+        const int64_t wide = labels[b * N + n];
+        const int label = wide >= 0 && wide < gt.n_cat && gt.cat_valid[wide] ? (int)wide : -1;
+        double ovmax = -INFINITY;
+        int jmax = -1;
+        if (label >= 0) {
+            const int32_t* cat = gt.cat + first;  // sorted within the image
+            int l = 0, r = G;
+            while (l < r) {
+                const int mid = (l + r) >> 1;
+                if (cat[mid] < label) l = mid + 1; else r = mid;
+            }
+            const float* c = boxes + (b * N + n) * 4;
+            const double d[4] = {(double)c[0], (double)c[1], (double)c[2], (double)c[3]};
+            for (int g = l; g < G && cat[g] == label; ++g) {
+                const double ov = voc_overlap(d, gt.box + (long)(first + g) * 4);
+                if (ov > ovmax) {  // strictly: the first row of the largest overlap stays
+                    ovmax = ov;
+                    jmax = g;
+                }
+            }
+        }
+        s_label[n] = label;
+        s_ov[n] = ovmax;
+        s_j[n] = jmax;
+    }
+    __syncthreads();
+    for (int n = threadIdx.x; n < N; n += kThreads) {
+        const int label = s_label[n], jmax = s_j[n];
+        const double ovmax = s_ov[n];
+        int flag = 0;
+        if (label >= 0) {
+            flag = 2;
+            if (ovmax > thr) {
+                flag = 1;
+                for (int m = 0; m < n; ++m)
+                    if (s_label[m] == label && s_j[m] == jmax && s_ov[m] > thr) flag = 3;
+            }
+        }
+        const long row = (long)img * N + n;
+        rec_flag[row] = (uint8_t)flag;
+        rec_gt[row] = jmax;
+        rec_iou[row] = ovmax;
+        rec_score[row] = scores[b * N + n];
+        rec_label[row] = (int32_t)labels[b * N + n];
+    }
+    if (threadIdx.x == 0) seen[img] = 1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -344,6 +423,19 @@ int grit_det_eval_img(const float* scores, const int64_t* labels, const float* b
     if (gt->max_per_img > kSide) return GRIT_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(det_eval_img_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, scores, labels, boxes, slot, N, *gt, iou_thr,
                        T, area_rng, A, rec_flags, rec_rank, rec_score, rec_label, seen);
+    return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
+}
+
+int grit_det_voc_img(const float* scores, const int64_t* labels, const float* boxes, const int32_t* slot, int B, int N,
+                     const grit_det_gt* gt, double iou_thr, uint8_t* rec_flag, int32_t* rec_gt, double* rec_iou, float* rec_score,
+                     int32_t* rec_label, uint8_t* seen, void* stream) {
+    if (!scores || !labels || !boxes || !slot || !gt || !rec_flag || !rec_gt || !rec_iou || !rec_score || !rec_label || !seen)
+        return GRIT_ERR_BAD_ARG;
+    if (!gt->img_off || !gt->box || !gt->cat || !gt->cat_valid || gt->n_img <= 0 || gt->n_cat <= 0) return GRIT_ERR_BAD_ARG;
+    if (B <= 0 || N <= 0 || N > kTop || iou_thr != iou_thr) return GRIT_ERR_BAD_ARG;
+    if (gt->max_per_img > kSide) return GRIT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(det_voc_img_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, scores, labels, boxes, slot, N, *gt, iou_thr,
+                       rec_flag, rec_gt, rec_iou, rec_score, rec_label, seen);
     return hipGetLastError() == hipSuccess ? GRIT_OK : GRIT_ERR_LAUNCH;
 }
 

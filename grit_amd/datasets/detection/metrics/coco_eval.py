@@ -27,7 +27,8 @@ class Params(object):
 
 class AnnotationIndex(object):
     """The four calls of the COCO API that the evaluation needs, over a dataset dictionary {'images': [{'id'}], 'categories':
-    [{'id'}], 'annotations': [{'id', 'image_id', 'category_id', 'bbox', 'area', 'iscrowd'}]}."""
+    [{'id'}], 'annotations': [{'id', 'image_id', 'category_id', 'bbox', 'area', 'iscrowd'}]}.  Further keys -- an annotation's
+    'attributes', an image's 'has_attr' -- pass through untouched."""
 
     def __init__(self, dataset):
         self.dataset = dataset
@@ -49,6 +50,11 @@ class AnnotationIndex(object):
 
     def loadAnns(self, ids=()):
         return [self.anns[i] for i in ids]
+
+    def loadImgs(self, ids=()):
+        """The image dictionaries as given ('has_attr' included), for the Visual Genome protocol's attribute split (vg_eval.py)."""
+        images = {i['id']: i for i in self.dataset['images']}
+        return [images[i] for i in ids]
 
 
 def accumulate_records(gt, rec_flags, rec_rank, rec_score, rec_label, seen, params):

@@ -95,14 +95,21 @@ MAP_KEYS = ('map', 'map50', 'map75', 'map_small', 'map_medium', 'map_large')  # 
 
 
 @torch.no_grad()
-def evaluate(model, criterion, postprocessors, batches, evaluator):
+def evaluate(model, criterion, postprocessors, batches, evaluator, vg_evaluator=None):
     """The reference's validation epoch (engine/det_solver.py:192-263) on one rank.  batches: an iterable of (samples, targets) on
     the device, every target with 'image_id' and 'orig_size'; evaluator: datasets.detection.metrics.CocoEvaluator.  Per batch:
     model -> criterion -> postprocessors['bbox'] -> evaluator.update, with no host synchronisation inside the loop; the records
     come to the host once, in evaluator.accumulate().  Returns {'losses': the mean weighted sum, every weighted loss's mean,
-    'bbox_map', 'bbox_map50', 'bbox_map75', 'bbox_map_small', 'bbox_map_medium', 'bbox_map_large', 'result_text'}."""
+    'bbox_map', 'bbox_map50', 'bbox_map75', 'bbox_map_small', 'bbox_map_medium', 'bbox_map_large', 'result_text'}.
+
+    vg_evaluator: a datasets.detection.metrics.VGEvaluator, fed in the same loop with the same 'bbox' results as its kind 'obj'
+    and, when it has the kind 'attr', with postprocessors['attr'](outputs, sizes) -- two more launches per batch, still no host
+    synchronisation.  The result gains 'vg_obj_map', 'vg_obj_wmap', 'vg_text' and, with 'attr', 'vg_attr_map', 'vg_attr_wmap'."""
     model.eval()
     criterion.eval()
+    if vg_evaluator is not None and 'attr' in vg_evaluator.kinds and 'attr' not in postprocessors:
+        raise ValueError("evaluate: the VG evaluator has the kind 'attr' but the model gives no attribute detections "
+                         "(postprocessors['attr'] comes with model.has_attr_head)")
     sums, steps = {}, 0
     for samples, targets in batches:
         outputs = model(samples)
@@ -111,8 +118,14 @@ def evaluate(model, criterion, postprocessors, batches, evaluator):
         weighted['losses'] = sum(weighted.values())
         for k, v in weighted.items():
             sums[k] = sums[k] + v.detach() if k in sums else v.detach()
-        results = postprocessors['bbox'](outputs, torch.stack([t['orig_size'] for t in targets], dim=0))
+        sizes = torch.stack([t['orig_size'] for t in targets], dim=0)
+        results = postprocessors['bbox'](outputs, sizes)
         evaluator.update(results, targets)
+        if vg_evaluator is not None:
+            vg_results = {'obj': results}
+            if 'attr' in vg_evaluator.kinds:
+                vg_results['attr'] = postprocessors['attr'](outputs, sizes)
+            vg_evaluator.update(vg_results, targets)
         steps += 1
     evaluator.synchronize_between_processes()
     evaluator.accumulate()
@@ -121,4 +134,12 @@ def evaluate(model, criterion, postprocessors, batches, evaluator):
     out = {k: float(v) / steps for k, v in sums.items()}
     out.update({'bbox_' + name: float(box.stats[i]) for i, name in enumerate(MAP_KEYS)})
     out['result_text'] = box.result_text
+    if vg_evaluator is not None:
+        vg_evaluator.synchronize_between_processes()
+        vg_evaluator.accumulate()
+        vg_evaluator.summarize()
+        for kind in vg_evaluator.kinds:
+            out['vg_%s_map' % kind] = float(vg_evaluator.stats[kind]['map'])
+            out['vg_%s_wmap' % kind] = float(vg_evaluator.stats[kind]['wmap'])
+        out['vg_text'] = vg_evaluator.result_text
     return out

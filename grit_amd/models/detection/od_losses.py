@@ -145,3 +145,22 @@ class PostProcess(nn.Module):
         top_logit, top_index, corners = _det_eval.det_topk(logits.float(), boxes.float(), target_sizes.float())
         scores, labels = top_logit.sigmoid(), top_index.to(torch.int64) % K
         return [{'scores': s, 'labels': l, 'boxes': b} for s, l, b in zip(scores, labels, corners)]
+
+
+class PostProcessAttr(nn.Module):
+    """Model outputs with 'attr_logits' [B, Q, A] -> per image the min(100, Q A) best (score, attribute, box): the attribute
+    detections of the Visual Genome protocol (datasets/detection/metrics/vg_eval.py).  The reference has no counterpart; this is
+    PostProcess on the attribute map -- grit_det_topk_f32 unchanged, score = the fp32 sigmoid of the selected logit, label = the
+    attribute index, box = that query's box as absolute corners."""
+
+    @torch.no_grad()
+    def forward(self, outputs, target_sizes):
+        if 'attr_logits' not in outputs:
+            raise ValueError("PostProcessAttr: the outputs have no 'attr_logits' (model.has_attr_head is off)")
+        logits, boxes = outputs['attr_logits'], outputs['pred_boxes']
+        if len(logits) != len(target_sizes) or target_sizes.shape[1] != 2:
+            raise ValueError("PostProcessAttr: target_sizes must be [batch, 2] (height, width)")
+        A = logits.shape[2]
+        top_logit, top_index, corners = _det_eval.det_topk(logits.float(), boxes.float(), target_sizes.float())
+        scores, labels = top_logit.sigmoid(), top_index.to(torch.int64) % A
+        return [{'scores': s, 'labels': l, 'boxes': b} for s, l, b in zip(scores, labels, corners)]

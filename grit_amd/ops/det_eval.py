@@ -6,9 +6,13 @@
     annotations sorted by category and in annotation order within a category.
   * `DeviceGroundTruth`, `EvalRecords`, `eval_images(...)`: the per-image matching launch and the record buffers it fills, which
     span the split and stay on the device until the accumulation copies them once.
+  * `pack_ground_truth_attr(dataset_like, num_attr)`, `VocRecords`, `voc_images(...)`: the same three steps for the Visual Genome
+    protocol (grit_det_voc_img): PASCAL-VOC matching at one threshold, for objects over pack_ground_truth's arrays and for
+    attributes over arrays in which an object stands once per attribute it carries.
 
-Nothing here reads a device value back.  Accumulation and summary: grit_amd/datasets/detection/metrics/coco_eval.py.
+Nothing here reads a device value back.  Accumulation and summary: grit_amd/datasets/detection/metrics/coco_eval.py and vg_eval.py.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -66,6 +70,47 @@ def pack_ground_truth(dataset_like):
                              np.asarray(ann_img, np.int32), np.asarray(ann_id, np.int64))
 
 
+def pack_ground_truth_attr(dataset_like, num_attr):
+    """The attribute split of the Visual Genome protocol as a PackedGroundTruth whose classes are the attributes 0 .. num_attr - 1:
+    an object contributes one row (class = a, its box) for every attribute a it carries, so the matching kernel is the same for
+    objects and attributes.  dataset_like: getImgIds(), getAnnIds(imgIds=[...]), loadAnns(ids) and loadImgs(ids); an annotation
+    carries 'attributes', a list of attribute ids (absent or empty: none; an id listed twice counts once), an image 'has_attr'
+    (absent: True).  An image with has_attr False is not part of the split (DeviceGroundTruth.slots_of gives it -1, so neither its
+    rows nor its detections count).  An image's rows are sorted by attribute and are in annotation order within an attribute;
+    area = w * h, crowd = 0, ann_id = the object's id.  ValueError for an attribute id outside [0, num_attr), for a split without
+    images and for an image with more than MAX_PER_IMAGE rows."""
+    num_attr = int(num_attr)
+    if num_attr <= 0:
+        raise ValueError("pack_ground_truth_attr: num_attr must be positive")
+    ids = sorted(int(i) for i in dataset_like.getImgIds())
+    if len(set(ids)) != len(ids):
+        raise ValueError("pack_ground_truth_attr: image ids are unique")
+    img_ids = [i for i in ids if dataset_like.loadImgs([i])[0].get('has_attr', True)]
+    if not img_ids:
+        raise ValueError("pack_ground_truth_attr: no image of the split has attributes")
+    img_off, box, cat, ann_img, ann_id = [0], [], [], [], []
+    for slot, img in enumerate(img_ids):
+        rows = []
+        for a in dataset_like.loadAnns(dataset_like.getAnnIds(imgIds=[img])):
+            for attr in sorted(set(int(v) for v in a.get('attributes', ()))):
+                if not 0 <= attr < num_attr:
+                    raise ValueError("pack_ground_truth_attr: attribute %d of annotation %s is outside [0, %d)" % (attr, a['id'], num_attr))
+                rows.append((attr, a))
+        if len(rows) > MAX_PER_IMAGE:
+            raise ValueError("pack_ground_truth_attr: image %d has %d attribute rows, the evaluation kernel takes %d"
+                             % (img, len(rows), MAX_PER_IMAGE))
+        for attr, a in sorted(rows, key=lambda r: r[0]):  # stable: annotation order within an attribute
+            box.append([float(v) for v in a['bbox']])
+            cat.append(attr)
+            ann_img.append(slot)
+            ann_id.append(int(a['id']))
+        img_off.append(len(cat))
+    box = np.asarray(box, np.float64).reshape(-1, 4)
+    return PackedGroundTruth(img_ids, np.arange(num_attr), np.asarray(img_off, np.int32), box, box[:, 2] * box[:, 3],
+                             np.asarray(cat, np.int32), np.zeros(len(cat), np.uint8), np.asarray(ann_img, np.int32),
+                             np.asarray(ann_id, np.int64))
+
+
 class DeviceGroundTruth(object):
     """A PackedGroundTruth on the device, and the grit_det_gt that points into it.  Every array has one padding element, so that
     a split without annotations is no null pointer."""
@@ -92,6 +137,19 @@ class DeviceGroundTruth(object):
         at = torch.searchsorted(self.img_ids, ids).clamp_(max=self.packed.n_img - 1)
         return torch.where(self.img_ids[at] == ids, at, torch.full_like(at, -1)).to(torch.int32)
 
+    def slots_for(self, image_ids):
+        """slots_of for whatever a batch carries: a tensor of ids or a list of 0-d tensors (looked up on the device, no
+        synchronisation), or a list of host integers (looked up on the host and uploaded)."""
+        import torch
+        if isinstance(image_ids, torch.Tensor):
+            return self.slots_of(image_ids.to(self.device))
+        if all(isinstance(i, torch.Tensor) for i in image_ids):
+            return self.slots_of(torch.stack([i.reshape(()) for i in image_ids]).to(self.device))
+        ids, wanted = self.packed.img_ids, np.asarray([int(i) for i in image_ids], np.int64)
+        at = np.minimum(np.searchsorted(ids, wanted), len(ids) - 1)
+        host = torch.from_numpy(np.where(ids[at] == wanted, at, -1).astype(np.int32))
+        return host.pin_memory().to(self.device, non_blocking=True)
+
 
 class EvalRecords(object):
     """The per-detection records of a split (include/grit_hip.h, grit_det_eval_img), on the device: flags [I * N, A] uint32 (as
@@ -110,6 +168,29 @@ class EvalRecords(object):
         """(flags uint32, rank, score, label, seen) as numpy arrays: the one device-to-host copy of an evaluation."""
         return (self.flags.cpu().numpy().view(np.uint32), self.rank.cpu().numpy(), self.score.cpu().numpy(), self.label.cpu().numpy(),
                 self.seen.cpu().numpy())
+
+
+VocHostRecords = collections.namedtuple("VocHostRecords", "flag gt iou score label seen")
+
+
+class VocRecords(object):
+    """The per-detection records of a split under the Visual Genome protocol (include/grit_hip.h, grit_det_voc_img), on the device:
+    flag [I * N] uint8 (0), gt [I * N] int32 (-1), iou [I * N] float64 (-inf), score [I * N] fp32 (0), label [I * N] int32 (-1),
+    seen [I] uint8 (0); in brackets what a row holds until its image has been matched."""
+
+    def __init__(self, n_img, n_det, device):
+        import torch
+        self.n_img, self.n_det = n_img, n_det
+        self.flag = torch.zeros(n_img * n_det, dtype=torch.uint8, device=device)
+        self.gt = torch.full((n_img * n_det,), -1, dtype=torch.int32, device=device)
+        self.iou = torch.full((n_img * n_det,), float('-inf'), dtype=torch.float64, device=device)
+        self.score = torch.zeros(n_img * n_det, dtype=torch.float32, device=device)
+        self.label = torch.full((n_img * n_det,), -1, dtype=torch.int32, device=device)
+        self.seen = torch.zeros(n_img, dtype=torch.uint8, device=device)
+
+    def to_host(self):
+        """VocHostRecords of numpy arrays: the one device-to-host copy of an evaluation."""
+        return VocHostRecords(*(getattr(self, name).cpu().numpy() for name in VocHostRecords._fields))
 
 
 def det_topk(logits, boxes, sizes):
@@ -166,3 +247,37 @@ def eval_images(scores, labels, boxes, slots, gt, iou_thr, area_rng, records):
                                            p(records.rank), p(records.score), p(records.label), p(records.seen),
                                            _lib.current_stream_ptr())
     _lib.check(st, "grit_det_eval_img")
+
+
+def voc_images(scores, labels, boxes, slots, gt, iou_thr, records):
+    """The matching of the Visual Genome protocol (grit_det_voc_img): scores [B, N] fp32, labels [B, N] int64, boxes [B, N, 4] fp32
+    absolute corners (an image's rows in score order), slots [B] int32; gt: DeviceGroundTruth of the object split
+    (pack_ground_truth) or of the attribute split (pack_ground_truth_attr); iou_thr: one host number (the protocol's 0.5) -> the
+    images' rows of `records` (VocRecords).  One launch, no synchronisation."""
+    import torch
+    _lib.require_device(scores, labels, boxes, slots)
+    if scores.dim() != 2:
+        raise _lib.GritHipError("det voc: scores [B, N], got %s" % (tuple(scores.shape),))
+    B, N = scores.shape
+    if tuple(labels.shape) != (B, N) or tuple(boxes.shape) != (B, N, 4) or tuple(slots.shape) != (B,):
+        raise _lib.GritHipError("det voc: scores / labels [B, N], boxes [B, N, 4], slots [B], got %s, %s, %s, %s"
+                                % (tuple(scores.shape), tuple(labels.shape), tuple(boxes.shape), tuple(slots.shape)))
+    if (scores.dtype, labels.dtype, boxes.dtype, slots.dtype) != (torch.float32, torch.int64, torch.float32, torch.int32):
+        raise _lib.GritHipError("det voc: scores fp32, labels int64, boxes fp32, slots int32")
+    if not isinstance(records, VocRecords) or N != records.n_det or records.n_img != gt.packed.n_img:
+        raise _lib.GritHipError("det voc: %d detections per image over %d images for VocRecords of %s and %s"
+                                % (N, gt.packed.n_img, getattr(records, 'n_det', None), getattr(records, 'n_img', None)))
+    if records.flag.device != scores.device or gt.img_off.device != scores.device:
+        raise _lib.GritHipError("det voc: detections, ground truth and records must be on one device")
+    iou_thr = float(iou_thr)
+    if iou_thr != iou_thr:
+        raise _lib.GritHipError("det voc: the overlap threshold is NaN")
+    if B == 0:
+        return
+    scores, labels, boxes, slots = (x if x.is_contiguous() else x.contiguous() for x in (scores, labels, boxes, slots))
+    p = _lib.ptr
+    with _lib.device_guard(scores.device):
+        st = _lib.load().grit_det_voc_img(p(scores), p(labels), p(boxes), p(slots), B, N, ctypes.c_void_p(ctypes.addressof(gt.struct)),
+                                          iou_thr, p(records.flag), p(records.gt), p(records.iou), p(records.score), p(records.label),
+                                          p(records.seen), _lib.current_stream_ptr())
+    _lib.check(st, "grit_det_voc_img")

@@ -86,7 +86,7 @@
 extern "C" {
 #endif
 
-#define GRIT_ABI_VERSION 61
+#define GRIT_ABI_VERSION 62
 
 #define GRIT_OK 0
 #define GRIT_ERR_BAD_ARG 1      /* null pointer, non-positive dimension, overflow of 32-bit index math      */
@@ -1280,6 +1280,27 @@ int grit_det_attr_bwd_f32(const float* attr_logits, const uint8_t* attributes, c
  *                                       cat_valid 0 (the detection does not take part)
  *     rec_score [n_img * N] fp32, rec_label [n_img * N] int32, seen [n_img] uint8 = 1
  * No atomics on global memory, no order dependence: two calls give identical bytes.
+ *
+ * grit_det_voc_img: the per-image matching of the Visual Genome protocol (reference datasets/detection/metrics/vg_eval.py:59-96:
+ * PASCAL-VOC matching at ONE overlap threshold, no difficult flags), one workgroup per image, the calling shape of
+ * grit_det_eval_img: scores, labels, boxes, slot, B, N <= GRIT_DET_TOPK and `gt` as above (area and crowd are not read and may be
+ * null; max_per_img > GRIT_DET_MAX_SIDE gives GRIT_ERR_UNSUPPORTED).  The same launch serves objects and attributes: for attributes
+ * the packer has written one row (class = attribute, box) per attribute an object carries.  For a detection with label c, over the
+ * image's rows of class c in packed order, all in float64, uncontracted, with the protocol's +1 pixel convention: bb = the fp32
+ * corners widened, g = (x, y, x + w, y + h) of the row's box,
+ *     iw = max(min(g2, bb2) - max(g0, bb0) + 1, 0), ih likewise, inters = iw ih,
+ *     uni = (bb2 - bb0 + 1)(bb3 - bb1 + 1) + (g2 - g0 + 1)(g3 - g1 + 1) - inters, ov = inters / uni;
+ * ovmax = the largest ov, jmax = the FIRST row that has it (a row replaces the held one only when its ov is greater, so a NaN
+ * overlap is never held); no rows: ovmax = -inf, jmax = -1.  The detection is a true positive iff ovmax > iou_thr (strictly) and no
+ * earlier detection of the image with the same label has the same jmax with ovmax > iou_thr; a later one with the same jmax is a
+ * duplicate.  That is a first-occurrence test over <= 100 detections: no loop that carries state from detection to detection.
+ * Records at row slot * N + n of buffers over the split:
+ *     rec_flag  [n_img * N] uint8       0: takes no part (label outside [0, n_cat) or cat_valid 0); 1: true positive;
+ *                                       2: false positive, no overlap (ovmax <= iou_thr); 3: false positive, duplicate
+ *     rec_gt    [n_img * N] int32       jmax as the row's index within the image, or -1
+ *     rec_iou   [n_img * N] float64     ovmax (-inf with rec_gt -1)
+ *     rec_score [n_img * N] fp32, rec_label [n_img * N] int32, seen [n_img] uint8 = 1
+ * iou_thr must not be NaN (GRIT_ERR_BAD_ARG).  No atomics, plain stores only: two calls give identical bytes.
  * ------------------------------------------------------------------------------------------------------ */
 #define GRIT_DET_TOPK 100
 #define GRIT_DET_TOPK_CHUNKS 40
@@ -1297,6 +1318,9 @@ int grit_det_topk_f32(const float* logits, const float* boxes, const float* size
 int grit_det_eval_img(const float* scores, const int64_t* labels, const float* boxes, const int32_t* slot, int B, int N,
                       const grit_det_gt* gt, const double* iou_thr, int T, const double* area_rng, int A, uint32_t* rec_flags,
                       int32_t* rec_rank, float* rec_score, int32_t* rec_label, uint8_t* seen, void* stream);
+int grit_det_voc_img(const float* scores, const int64_t* labels, const float* boxes, const int32_t* slot, int B, int N,
+                     const grit_det_gt* gt, double iou_thr, uint8_t* rec_flag, int32_t* rec_gt, double* rec_iou, float* rec_score,
+                     int32_t* rec_label, uint8_t* seen, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * JPEG decoding (DESIGN "JPEG decoding"): baseline files -> the [h, w, 3] uint8 RGB pixels of libjpeg-turbo's defaults (JDCT_ISLOW,

@@ -1,6 +1,6 @@
 """Detector pre-training, the first stage of the published recipe (the reference's train_detector.py).
 
-    python train_detector.py --synthetic [--augment] [--attr] --steps 3 [--batch-size 2] [--size 224] [--bf16] [--eval] [key=value ...]
+    python train_detector.py --synthetic [--augment] [--attr] --steps 3 [--batch-size 2] [--size 224] [--bf16] [--eval [--eval-protocol vg]] [key=value ...]
 
 The Visual Genome / LMDB readers and the hook-based solver are out of scope of this build, so the only data source here is
 `--synthetic`: seeded random images and targets.  It runs the real model, the device matcher and criterion
@@ -15,6 +15,9 @@ multi-hot attributes, attr_loss_coef is 1, the head has its own AdamW (optimizer
 with the other losses.
 `--eval` evaluates after the steps (engine.det_engine.evaluate: PostProcess and the COCO-style box evaluation on the device,
 datasets.detection.metrics.CocoEvaluator) on `--eval-batches` seeded synthetic batches and prints the losses and the box mAP table.
+`--eval-protocol vg` (default `coco`) also runs the Visual Genome protocol in the same loop (datasets.detection.metrics.VGEvaluator:
+PASCAL-VOC AP at IoU 0.5 per class) and prints the mean and the weighted mean AP over the object classes and, with `--attr`, over the
+attribute classes (PostProcessAttr's detections; the split's targets then carry attributes on every other image).
 Configuration: grit_amd.config.detection_config (the keys of configs/detection/train_config.yaml), dotted key=value overrides.
 """
 import argparse
@@ -53,20 +56,30 @@ def add_synthetic_attributes(generator, targets, num_attr, device):
     return targets
 
 
-def synthetic_split(generator, batches, batch_size, size, num_classes, max_targets, device):
+def synthetic_split(generator, batches, batch_size, size, num_classes, max_targets, device, num_attr=0):
     """`batches` synthetic batches as an evaluation split: every target also carries 'image_id' and 'orig_size' (device tensors),
-    and the annotations -- the same boxes in pixels, (x, y, w, h), area w * h, ids from 1 -- come back as a COCO dataset dictionary."""
+    and the annotations -- the same boxes in pixels, (x, y, w, h), area w * h, ids from 1 -- come back as a COCO dataset dictionary.
+    With num_attr > 0 the targets carry attributes as the training batches do (add_synthetic_attributes: every other image), the
+    images of the dictionary 'has_attr' and the annotations 'attributes', the list of an object's attribute ids."""
     split, images, annotations = [], [], []
     for _ in range(batches):
         samples, targets = synthetic_batch(generator, batch_size, size, num_classes, max_targets, device)
+        if num_attr > 0:
+            add_synthetic_attributes(generator, targets, num_attr, device)
         for t in targets:
             image_id = len(images) + 1
             images.append({'id': image_id, 'height': size, 'width': size})
             t['image_id'] = torch.tensor(image_id, device=device)
             t['orig_size'] = torch.tensor([size, size], device=device)
+            first = len(annotations)
             for label, (cx, cy, w, h) in zip(t['labels'].tolist(), (t['boxes'].double() * size).tolist()):
                 annotations.append({'id': len(annotations) + 1, 'image_id': image_id, 'category_id': label,
                                     'bbox': [cx - 0.5 * w, cy - 0.5 * h, w, h], 'area': w * h, 'iscrowd': 0})
+            if num_attr > 0:
+                images[-1]['has_attr'] = bool(t['has_attr'])
+                if t['has_attr']:
+                    for ann, row in zip(annotations[first:], t['attributes'].tolist()):
+                        ann['attributes'] = [a for a, on in enumerate(row) if on]
         split.append((samples, targets))
     return split, {'images': images, 'categories': [{'id': c} for c in range(num_classes)], 'annotations': annotations}
 
@@ -112,6 +125,9 @@ def main():
                     help='with --bf16: step the lr schedulers once per this many steps (0: never within a run)')
     ap.add_argument('--eval', action='store_true', help='after the steps: losses and COCO-style box mAP on seeded synthetic batches')
     ap.add_argument('--eval-batches', type=int, default=2)
+    ap.add_argument('--eval-protocol', choices=('coco', 'vg'), default='coco',
+                    help="with --eval: 'vg' adds the Visual Genome protocol (VOC AP at IoU 0.5: mean and weighted mean over the object "
+                         'classes and, with --attr, over the attribute classes; the split then carries attributes on every other image)')
     ap.add_argument('overrides', nargs='*', help='dotted key=value configuration overrides')
     args = ap.parse_args()
     if not args.synthetic:
@@ -163,9 +179,17 @@ def main():
                 sch.step()
     if args.eval:
         from datasets.detection.metrics import AnnotationIndex, CocoEvaluator
-        split, dataset = synthetic_split(g, args.eval_batches, batch_size, args.size, config.model.det_module.num_classes, args.max_targets, device)
-        result = evaluate(model, criterion, postprocessors, split, CocoEvaluator(AnnotationIndex(dataset), ('bbox',), device=device))
-        text = result.pop('result_text')
+        vg = args.eval_protocol == 'vg'
+        num_attr = config.model.num_attr_classes if vg and args.attr else 0
+        split, dataset = synthetic_split(g, args.eval_batches, batch_size, args.size, config.model.det_module.num_classes, args.max_targets,
+                                         device, num_attr=num_attr)
+        index = AnnotationIndex(dataset)
+        vg_evaluator = None
+        if vg:
+            from datasets.detection.metrics import VGEvaluator
+            vg_evaluator = VGEvaluator(index, ('obj', 'attr') if args.attr else ('obj',), num_attr=num_attr, device=device)
+        result = evaluate(model, criterion, postprocessors, split, CocoEvaluator(index, ('bbox',), device=device), vg_evaluator=vg_evaluator)
+        text = result.pop('result_text') + result.pop('vg_text', '')
         print('eval  %s' % {k: round(v, 5) for k, v in sorted(result.items())})
         print(text, end='')
 
