@@ -5,7 +5,8 @@
     python tools/micro/wb_stamps_patch.py restore   # puts the product source back and rebuilds
 
 The stamps add a global symbol and ~40 scalar instructions per window: never commit the patched source.  The anchors are source
-lines of the kernel; the script asserts each of them, so it fails loudly when the kernel has moved on."""
+lines of the kernel body (its phase boundaries: waits, barriers and the calls of the shared stages); the script asserts each of them, so
+it fails loudly when the kernel has moved on."""
 import os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -16,7 +17,7 @@ def apply():
     shutil.copy(SRC, SRC + ".orig")
     p = SRC
     s=open(p).read()
-    i=s.index('template <bool kExplicitMask>\n__global__ __launch_bounds__(kThreads)\nvoid winattn_bwd_dma(')
+    i=s.index('template <bool kExplicitMask, bool kSkip = false>\n__global__ __launch_bounds__(kThreads)\nvoid winattn_bwd_dma(')
     head, body = s[:i], s[i:]
     st = {'body': body}
     head+="__device__ unsigned long long g_wb_stamps[256];\n#define WB_ST(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); st[k] += now_ - tprev; tprev = now_; }\n"
@@ -29,13 +30,12 @@ def apply():
     rep("        __syncthreads();  // statistics visible; the V / O tiles and the other tile buffer are free for the next window's DMA\n",
       "        WB_ST(3)\n        __syncthreads();  // statistics visible; the V / O tiles and the other tile buffer are free for the next window's DMA\n        WB_ST(4)\n")
     rep("        // Per-lane LDS offsets, made opaque once per window","        WB_ST(5)\n        // Per-lane LDS offsets, made opaque once per window")
-    rep("        if (tkk >= 0) {\n            __bf16* base = dqkv + (img + tkk) * C3 + hoff + 4 * lg;\n            v4bf a, c, e, f;",
-      "        WB_ST(6)\n        if (tkk >= 0) {\n            __bf16* base = dqkv + (img + tkk) * C3 + hoff + 4 * lg;\n            v4bf a, c, e, f;")
+    rep("        bwd_store_dkdv(dqkv, pad_s,", "        WB_ST(6)\n        bwd_store_dkdv(dqkv, pad_s,")
     rep("        __syncthreads();  // dSt complete\n","        WB_ST(7)\n        __syncthreads();  // dSt complete\n        WB_ST(8)\n")
-    rep("    // ---- flush the register-resident d(bias) of this workgroup's windows and the padded-token gradient",
-      "    if (lane == 0) { for (int k = 0; k < 10; ++k) atomicAdd(&g_wb_stamps[w * 16 + k], st[k]); atomicAdd(&g_wb_stamps[w * 16 + 10], 1ull); }\n    // ---- flush the register-resident d(bias) of this workgroup's windows and the padded-token gradient")
-    rep("                if (l15 == 0) {\n                    atomicAdd(&pad_s[4 * lg + r], a);\n                    atomicAdd(&pad_s[16 + 4 * lg + r], c);\n                }\n            }\n        }\n    }\n",
-      "                if (l15 == 0) {\n                    atomicAdd(&pad_s[4 * lg + r], a);\n                    atomicAdd(&pad_s[16 + 4 * lg + r], c);\n                }\n            }\n        }\n        WB_ST(9)\n    }\n")
+    rep("    bwd_flush_dbias(dbias, dB, h, w, l15, lg);",
+      "    if (lane == 0) { for (int k = 0; k < 10; ++k) atomicAdd(&g_wb_stamps[w * 16 + k], st[k]); atomicAdd(&g_wb_stamps[w * 16 + 10], 1ull); }\n    bwd_flush_dbias(dbias, dB, h, w, l15, lg);")
+    rep("        bwd_store_dq(dqkv, pad_s, g, img, tkk, C3, hoff, l15, lg, dq0, dq1);\n    }\n",
+      "        bwd_store_dq(dqkv, pad_s, g, img, tkk, C3, hoff, l15, lg, dq0, dq1);\n        WB_ST(9)\n    }\n")
     s = head + st['body']
     s+="\nextern \"C\" int grit_debug_winattn_stamps(unsigned long long* out, int reset) {\n    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wb_stamps), sizeof(unsigned long long) * 256) != hipSuccess) return -1;\n    if (reset) { unsigned long long z[256] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_wb_stamps), z, sizeof(z)) != hipSuccess) return -1; }\n    return 0;\n}\n"
     open(p,'w').write(s)
