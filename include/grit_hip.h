@@ -1167,6 +1167,7 @@ int grit_caption_scores(const int64_t* tokens, int rows, int T, const int32_t* s
  *     match_q [P, Tmax] int32: the query of each target, -1 for an unmatched target and for t >= T
  *     match_t [P, Q]    int32: the target (index within its image) of each query, or -1
  * A label outside [0, K) or a non-finite cost that leaves a row without a finite path leaves the whole problem unmatched (-1).
+ * A cost of -inf is outside the contract (scipy refuses it too): what a problem that holds one comes back with is unspecified.
  * BOUND: Q <= GRIT_DET_MAX_SIDE and Tmax <= GRIT_DET_MAX_SIDE (the O(Q + T) solver state of a problem lives in 19 KB of LDS);
  * above it GRIT_ERR_UNSUPPORTED.  An image with more than Tmax targets comes back unmatched.  Tmax >= 1 (pass 1 for an empty batch).
  *
